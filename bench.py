@@ -1,6 +1,6 @@
 """bench.py — denoise-steps/sec of the MoviiGen1.1 14B T2V hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 1080p|720p|1056p|tiny]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 1080p|720p|1056p|tiny] [--dump-outputs DIR] [--full]
 
 One "step" = what one iteration of the reference loop does (wan/text2video.py:233-254):
 two WanModel forwards (cond / uncond), the CFG combine and one UniPC scheduler step, on
@@ -20,7 +20,10 @@ scripts/inference/generate.py:190-229, one process per GPU + init_process_group(
 reports what RCCL saw: `rccl_ranks`, the device of every rank, the transport and the measured overlap (fraction of the
 exchange time the compute stream did NOT wait for, from events on both streams).
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (self-attention, 82 % of
+Prints ONE JSON line (rank 0).  A plain run does only what `value` / `ms_per_step` need: set-up, W warm-up steps, K timed
+steps, the line.  Everything else it measures runs with `--full` only (for N > 1 also the preflight, the second layout and the
+exchange / gather traces; N = 1 box calibration and telemetry likewise):
+`roofline` is for the dominant kernel (self-attention, 82 % of
 the FLOPs at this size): algorithmic FLOPs per launch / mean launch duration, measured live with
 events on the launch stream during the timed region.  After the timed region the same process
 measures what is left of `sec/video` (reference wan/text2video.py:228-261): the WanVAE decode of a
@@ -28,6 +31,8 @@ latent of the workload's size and (reported separately, as SURVEY.md §8(d) pres
 umT5-XXL prompt encodes; `sec_per_video` = 50 x the measured step + the measured decode.
 `cpu_baseline` times the ORACLE (oracle/dit.py, oracle/vae.py: the CPU restatements) on bounded
 slices on this box's host cores and extrapolates by the FLOP formulas (rule stated in the line).
+`--dump-outputs DIR` writes what the last timed step computed (write_outputs) so that two builds can be compared output for
+output: the inputs and weights are seeded, identical from run to run for the same arguments.
 """
 import argparse
 import json
@@ -282,6 +287,19 @@ def measure_attention_traffic(L, heads, timeout=240):
             'dispatches': [kib['FETCH_SIZE'][1], kib['WRITE_SIZE'][1]]}, None
 
 
+def write_outputs(out_dir, latent, noise_pred, sample=1 << 20):
+    """--dump-outputs: what the timed path computed in its last step, as float32 .npy files (47 MB in all at the largest workload):
+      latent.npy      the latent that step returns, [16, T, h, w] in full (33.5 MB at 1080p, 42.6 MB at 1056p);
+      noise_pred.npy  the CFG-combined noise prediction of that step (same shape) as a fixed sample of `sample` elements, 1-D:
+                      flat indices numpy.random.default_rng(0).choice(numel, sample, replace=False), sorted."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'latent.npy'), latent.float().cpu().numpy())
+    flat = noise_pred.float().reshape(-1).cpu().numpy()
+    idx = np.sort(np.random.default_rng(0).choice(flat.size, min(flat.size, sample), replace=False))
+    np.save(os.path.join(out_dir, 'noise_pred.npy'), flat[idx])
+
+
 def launch_command(n, argv, port=None):
     """the torch.distributed.run command line `python bench.py --gpus n ...` re-executes itself under when it is
     started without WORLD_SIZE (one rank per GPU of this node, rendezvous on 127.0.0.1)."""
@@ -340,11 +358,18 @@ def main():
     ap.add_argument('--gemm-variant', type=int, default=0,
                     help='A/B only: force a tile schedule of mg_gemm_bf16 (same bits; 0 = the library default by shape, 8 = the round-3 '
                          'default); recorded in config.gemm_variant')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything besides the headline step time: box calibration, telemetry, the live attention roofline, the '
+                         'forward_pair leg, the sec/video tail (VAE decode, T5), the HBM traffic passes, the CPU baseline; N > 1: the preflight, '
+                         'the second layout and the exchange / gather traces.  The --no-* flags above switch parts of it off')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32, see write_outputs)')
     args = ap.parse_args()
     if args.emulate_rank:
+        import subprocess
         cmd = [sys.executable, os.path.join(ROOT, 'tools', 'emulate_rank.py'), '--workload', args.workload if args.workload in ('720p', '1080p', '1056p') else '1080p',
                '--ranks', str(args.emulate_rank), '--steps', str(args.steps), '--fsdp-at'] + ([str(args.emulate_rank)] if args.dit_fsdp else [])
-        os.execv(sys.executable, cmd)
+        sys.exit(subprocess.call(cmd))
     if args.transport is not None:        # read by wan.distributed at exchange-construction time; inherited by self-launched ranks
         os.environ['MOVIIGEN_SP_TRANSPORT'] = args.transport
 
@@ -392,12 +417,13 @@ def main():
     if args.gemm_variant:
         from wan.backend import lib as _lib
         _lib.ab_library().__enter__().mg_gemm_set_variant(args.gemm_variant)      # measurement only: the whole process runs on the A/B library
+    full = args.full
     calib = None
-    if world == 1 and not args.no_calibration and args.workload != 'tiny' and not args.layers:
+    if full and world == 1 and not args.no_calibration and args.workload != 'tiny' and not args.layers:
         calib = box_calibration(dev, local)
     # ---- N > 1: what this node / process group can do, measured before anything else (wan/distributed/preflight.py) -------------------
     pre = None
-    if world > 1 and not args.no_preflight:
+    if full and world > 1 and not args.no_preflight:
         from wan.distributed import preflight
         want_peer = (args.transport or os.environ.get('MOVIIGEN_SP_TRANSPORT') or 'torch') in ('auto', 'peer_copy') or args.preflight == 'full'
         try:
@@ -416,7 +442,7 @@ def main():
     even = world > 1 and world % 2 == 0
     primary = 'single' if world == 1 else 'cfg' if even and (args.cfg_parallel or args.dit_fsdp) and not args.no_cfg_parallel else 'ulysses'
     secondary = None
-    if even and not args.single_layout and not args.dit_fsdp:
+    if full and even and not args.single_layout and not args.dit_fsdp:
         secondary = 'ulysses' if primary == 'cfg' else 'cfg'
 
     g = torch.Generator(device=dev).manual_seed(42)
@@ -439,7 +465,8 @@ def main():
             attn_events.append((a, b, heads))
             return r
         return orig_attn(q, k, vt, out, lk, heads, scale, **kw)
-    ops.attention_hd128 = timed_attn
+    if full:
+        ops.attention_hd128 = timed_attn
 
     def fence():
         torch.cuda.synchronize()
@@ -468,7 +495,7 @@ def main():
                 from wan.distributed.fsdp import shard_model
                 shard_model(model, device_id=local)       # 1/N of every block's GEMM weights per rank, gathered one block ahead
         sch = FlowUniPCMultistepScheduler(num_train_timesteps=1000, shift=1, use_dynamic_shifting=False)
-        sch.set_timesteps(50, device=dev, shift=5.0)
+        sch.set_timesteps(max(50, total), device=dev, shift=5.0)      # the reference's 50 steps; more only when W + K asks for more
         ts = sch.timesteps
         ts_host = ts.tolist()
         st = {'latent': latent0.clone()}
@@ -489,31 +516,33 @@ def main():
         for i in range(args.warmup):
             step(i)
         fence()
-        if world > 1:
+        if world > 1 and full:
             HeadExchange.trace = []          # events around every collective / every wait of the compute stream on one
             if args.dit_fsdp:
                 BlockShards.trace = []
         recording['on'] = is_primary
-        tel = _telemetry(local).start() if rank == 0 else None        # a thread reading sysfs through libamd_smi twice a second: nothing in the GPU's way
+        tel = _telemetry(local).start() if rank == 0 and full else None        # a thread reading sysfs through libamd_smi twice a second: nothing in the GPU's way
         t0 = time.perf_counter()
         for i in range(args.warmup, total):
             step(i)
         fence()
         elapsed = time.perf_counter() - t0
         R = {'layout': layout, 'model': model, 'cfgp': cfgp, 'sp': model.sp_size, 'telemetry': tel.stop() if tel is not None else None,
-             'overlap': None, 'fsdp_trace': None, 'sp_groups': None, 'peer_used': False}
+             'overlap': None, 'fsdp_trace': None, 'sp_groups': None, 'peer_used': False,
+             'noise_pred': noise_pred.clone() if args.dump_outputs and is_primary else None}   # (the forward_pair leg below reuses the buffer)
         recording['on'] = False
         if world > 1:
             tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = tt.item()
-            R['overlap'] = HeadExchange.overlap_summary()
-            HeadExchange.trace = None
+            if full:
+                R['overlap'] = HeadExchange.overlap_summary()
+                HeadExchange.trace = None
             R['peer_used'] = any('xchg' in w_ and w_['xchg'].peer is not None for w_ in model._ws.values())
             xchgs = [w_['xchg'] for w_ in model._ws.values() if 'xchg' in w_]
             R['sp_groups'] = {'heads_per_group': [n for _, n in xchgs[0].groups], 'attention_rounds_per_layer': xchgs[0].rounds,
                               'chosen_by': os.environ.get('MOVIIGEN_SP_GROUPS', '') or 'auto'} if xchgs else None
-            if args.dit_fsdp:
+            if args.dit_fsdp and full:
                 from wan.distributed.collectives import trace_summary
                 R['fsdp_trace'] = trace_summary(BlockShards.trace)
                 BlockShards.trace = None
@@ -523,7 +552,7 @@ def main():
         # computed once for the two guidance branches.  Its own short leg AFTER the timed region — `value` stays the two plain forwards.
         R['shared_prefix'] = None
         k2 = min(args.steps, 2, 50 - total)
-        if cfgp is None and is_primary and k2 > 0 and not args.no_shared_prefix_leg:
+        if full and cfgp is None and is_primary and k2 > 0 and not args.no_shared_prefix_leg:
             def step_pair(i):
                 latent = st['latent']
                 t = ts[i:i + 1]
@@ -555,6 +584,9 @@ def main():
         return R
 
     R = measure(primary, True)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, R['latent'], R['noise_pred'])
+    R['noise_pred'] = None
     other = None
     if secondary is not None:
         # the second layout of the same video on the same ranks, its own warm-up and K timed steps; the primary's model is released first
@@ -590,7 +622,7 @@ def main():
     # separately, the two umT5-XXL prompt encodes.  Random-init weights of the shipped architectures.
     vae_s = t5_s = None
     vae_pipe = args.vae_parallel if world > 1 else None       # None | 'spatial' | 'pipeline'
-    if (rank == 0 or vae_pipe) and not args.no_video_tail:
+    if full and (rank == 0 or vae_pipe) and not args.no_video_tail:
         import weights as Wt
         z = latent.clone()
         model._ws = {}                       # the DiT activations are not needed any more
@@ -616,7 +648,7 @@ def main():
             assert video.shape == (3, frames, Hd, Wd) and torch.isfinite(video).all().item()
         del video, vae
         torch.cuda.empty_cache()
-    if rank == 0 and not args.no_video_tail:
+    if full and rank == 0 and not args.no_video_tail:
         if not args.layers and args.workload != 'tiny':
             from wan.modules.t5 import umt5_xxl
             enc = umt5_xxl(device=dev)
@@ -663,25 +695,27 @@ def main():
                        'parallelism': R['parallelism'], 'solver': 'unipc',
                        'guide_scale': 5.0, 'weights': 'random N(0,0.02) bf16, seed 0',
                        **({'gemm_variant': args.gemm_variant} if args.gemm_variant else {})},
-            'sec_per_video': (ms_step * 50 / 1e3 + vae_s) if vae_s is not None else None,
-            'shared_prefix': R['shared_prefix'],
-            'sec_per_video_shared_prefix': (R['shared_prefix']['ms_per_step'] * 50 / 1e3 + vae_s) if vae_s is not None and R['shared_prefix'] else None,
-            'sec_per_video_parts': {'denoise_50_steps_s': ms_step * 50 / 1e3, 'vae_decode_s': vae_s,
-                                    't5_encode_2_prompts_s_not_included': t5_s,
-                                    'note': '50 x the measured step + the measured WanVAE.decode of this latent size, same '
-                                            'process; T5 reported separately (SURVEY 8(d))'},
             'model_tflops_per_gpu': fl_step / (elapsed / args.steps) / world / 1e12,
             'mfma_frac_whole_step': fl_step / (elapsed / args.steps) / world / PEAK_BF16,
-            'roofline': {'kernel': 'attn_hd128_m16_kernel (self-attention, mg_attn_fwd_bf16_hd128_prescaled)', 'bound': 'mfma',
-                         'achieved': ach, 'peak': PEAK_BF16 / 1e12, 'unit': 'TFLOP/s',
-                         'frac': (ach * 1e12 / PEAK_BF16) if ach else None, 'traffic': None,
-                         'launches_timed': len(attn_events), 'ms_per_launch': attn_ms,
-                         'algorithmic_flops_per_launch': attn_flops},
         }
-        # clock / power / temperature of the timed region and the firmware's own account of what held the clock (PPT = package power
-        # tracking, thermal, VR, HBM, PROCHOT residencies: fraction of the interval each limiter was active), + what this box sustains on
-        # the two hot kernels alone: without them a slow box and a slow build are indistinguishable
-        line['telemetry'] = telemetry
+        if full:
+            line.update({
+                'sec_per_video': (ms_step * 50 / 1e3 + vae_s) if vae_s is not None else None,
+                'shared_prefix': R['shared_prefix'],
+                'sec_per_video_shared_prefix': (R['shared_prefix']['ms_per_step'] * 50 / 1e3 + vae_s) if vae_s is not None and R['shared_prefix'] else None,
+                'sec_per_video_parts': {'denoise_50_steps_s': ms_step * 50 / 1e3, 'vae_decode_s': vae_s,
+                                        't5_encode_2_prompts_s_not_included': t5_s,
+                                        'note': '50 x the measured step + the measured WanVAE.decode of this latent size, same '
+                                                'process; T5 reported separately (SURVEY 8(d))'},
+                'roofline': {'kernel': 'attn_hd128_m16_kernel (self-attention, mg_attn_fwd_bf16_hd128_prescaled)', 'bound': 'mfma',
+                             'achieved': ach, 'peak': PEAK_BF16 / 1e12, 'unit': 'TFLOP/s',
+                             'frac': (ach * 1e12 / PEAK_BF16) if ach else None, 'traffic': None,
+                             'launches_timed': len(attn_events), 'ms_per_launch': attn_ms,
+                             'algorithmic_flops_per_launch': attn_flops},
+                # clock / power / temperature of the timed region and the firmware's own account of what held the clock (PPT = package power
+                # tracking, thermal, VR, HBM, PROCHOT residencies: fraction of the interval each limiter was active), + what this box sustains on
+                # the two hot kernels alone (below): without them a slow box and a slow build are indistinguishable
+                'telemetry': telemetry})
         if calib is not None:
             line['box_attn_tflops'] = calib['attn']['tflops']
             line['box_gemm_tflops'] = calib['gemm_ffn0']['tflops']
@@ -696,7 +730,7 @@ def main():
         # over the same launch shape (measure_attention_traffic); only when that is impossible (--no-pmc, no rocprofv3)
         # the newest committed summary for this workload is reported instead, and labelled as such — never a guess
         live = None
-        if world == 1 and not args.layers and not args.no_pmc and args.workload != 'tiny':
+        if full and world == 1 and not args.layers and not args.no_pmc and args.workload != 'tiny':
             live, why = measure_attention_traffic(L, cfg['num_heads'])
             if live is not None:
                 line['roofline']['traffic'] = live['traffic_bytes_per_launch']
@@ -705,7 +739,7 @@ def main():
                 line['roofline']['algorithmic_bytes_per_launch'] = 4 * L * cfg['dim'] * 2
             else:
                 line['roofline']['traffic_live_failed'] = why
-        if world == 1 and not args.layers and live is None:
+        if full and world == 1 and not args.layers and live is None:
             import glob
             found = sorted(glob.glob(os.path.join(ROOT, 'profiles', f'*pmc_traffic_{args.workload}.json')))
             if not found and args.workload == '720p':
@@ -754,13 +788,13 @@ def main():
                                    'hidden_frac': overlap['hidden_frac'], 'collectives_per_step': overlap['collectives'] * per,
                                    'how': 'rank 0: timing events around every all-to-all on the comm stream (exchange) and around every '
                                           'wait of the compute stream on the comm stream (exposed); hidden = 1 - exposed / exchange'}
-            else:
+            elif full:
                 line['overlap'] = None      # no per-layer exchange in this layout (e.g. cfg2 on 2 ranks: one forward per rank)
         if os.environ.get('MOVIIGEN_BENCH_BACKEND') == 'gloo':
             line['invalid'] = 'gloo test transport on a shared GPU (code-path check, not a measurement)'
         if args.layers or args.workload == 'tiny':
             line['invalid'] = 'debug configuration (not the BASELINE model)'
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(L, lat_shape)
         print(json.dumps(line), flush=True)
     if world > 1:

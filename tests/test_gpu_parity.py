@@ -1769,7 +1769,7 @@ def test_bench_multirank_code_path(world, extra, plain):
     env = dict(os.environ, MOVIIGEN_BENCH_BACKEND='gloo')
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
-    tail = [os.path.join(root, 'bench.py'), '--gpus', str(world), '--steps', '1', '--warmup', '1', '--workload', 'tiny'] + extra
+    tail = [os.path.join(root, 'bench.py'), '--gpus', str(world), '--steps', '1', '--warmup', '1', '--workload', 'tiny', '--full'] + extra
     head = [sys.executable] if plain else [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={world}',
                                            '--master-addr', '127.0.0.1', '--master-port', str(29590 + world + len(extra))]
     r = subprocess.run(head + tail, capture_output=True, text=True, timeout=900, env=env)
@@ -1910,6 +1910,40 @@ def test_bench_refuses_more_ranks_than_gpus():
                         '--workload', 'tiny'], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode != 0
     assert 'needs 2 visible GPUs' in (r.stdout + r.stderr), (r.stdout + r.stderr)[-2000:]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` times K steps and reports nothing that needs a leg of its own (those run with
+    --full), and --dump-outputs writes what the last timed step computed: float32, the same bits with --full as without
+    (the extra legs leave the timed path alone; the inputs are seeded)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MOVIIGEN_BENCH_BACKEND')}
+    lines, dumps = [], []
+    for i, extra in enumerate(([], ['--full', '--no-cpu-baseline'])):
+        out = tmp_path / f'out{i}'
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--workload', 'tiny',
+                            '--dump-outputs', str(out)] + extra, capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        js = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+        assert len(js) == 1, r.stdout[-2000:]
+        lines.append(json.loads(js[0]))
+        dumps.append({n: np.load(out / f'{n}.npy') for n in ('latent', 'noise_pred')})
+        assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64e6
+    plain, full = lines
+    assert plain['steps'] == 2 and plain['warmup'] == 1 and plain['ms_per_step'] > 0 and abs(plain['value'] * plain['ms_per_step'] - 1e3) < 1e-6
+    assert plain['metric'] == full['metric'] == 'denoise-steps/sec' and plain['dtype'] == 'bf16' and plain['higher_is_better'] is True
+    for k in ('roofline', 'sec_per_video', 'telemetry', 'vae_decode', 'cpu_baseline'):
+        assert k not in plain, k
+    assert 'roofline' in full and 'vae_decode' in full
+    lat = dumps[0]['latent']
+    assert lat.dtype == np.float32 and lat.shape == tuple(plain['config']['latent']) and np.isfinite(lat).all()
+    assert dumps[0]['noise_pred'].dtype == np.float32 and dumps[0]['noise_pred'].size == lat.size
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
 
 
 def test_rccl_backend_single_rank():

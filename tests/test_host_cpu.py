@@ -405,6 +405,25 @@ def test_bench_flop_formulas():
     assert b.WORKLOADS['1080p'][:3] == (1920, 832, 81)
 
 
+def test_bench_write_outputs(tmp_path):
+    """bench.py --dump-outputs: the latent in full, the noise prediction as the fixed sample write_outputs documents; float32,
+    and within 64 MB at the largest workload."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    g = torch.Generator().manual_seed(0)
+    lat, pred = torch.randn(16, 3, 12, 16, generator=g), torch.randn(16, 3, 12, 16, generator=g)
+    b.write_outputs(str(tmp_path / 'o'), lat, pred, sample=1000)
+    got = np.load(tmp_path / 'o' / 'latent.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, lat.numpy())
+    idx = np.sort(np.random.default_rng(0).choice(lat.numel(), 1000, replace=False))
+    got = np.load(tmp_path / 'o' / 'noise_pred.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, pred.numpy().reshape(-1)[idx])
+    Wd, Hd, frames, _ = max(b.WORKLOADS.values(), key=lambda w: w[0] * w[1] * w[2])
+    assert 4 * (16 * ((frames - 1) // 4 + 1) * (Hd // 8) * (Wd // 8) + (1 << 20)) <= 64e6
+
+
 def test_bench_self_launch_command():
     """`python bench.py --gpus N` without WORLD_SIZE becomes the launcher of its own ranks (reference launch contract
     scripts/inference/generate.py:190-229: one process per GPU): the command it re-executes, checked without running it."""

@@ -2,19 +2,19 @@
 # Scaling sweep of the metric on ONE node with N visible GPUs: bench.py at 1 / 2 / 4 / 8 ranks and the three transports of the exchange.  Since round 6 ONE
 # bench.py run measures both layouts of the multi-GPU forward (primary = Ulysses over all ranks, the reference's layout = BASELINE configs[2]; `other_layout` =
 # cond / uncond halves x Ulysses N/2) and starts with the preflight (ranks, peer access, a 64 MiB all-to-all; with --transport peer_copy also the IPC windows and
-# the same exchange as peer copies -> link_gbps_measured, transport_recommended).  One JSON line per run is appended to gpurun_out/scale_sweep_<tag>.jsonl, and a
+# the same exchange as peer copies -> link_gbps_measured, transport_recommended).  One JSON line per run is appended to $OUT_DIR/scale_sweep_<tag>.jsonl (default results/), and a
 # table is printed at the end.  Nothing here could be run by the builder (1-GPU boxes); it needs nothing but visible GPUs.
 # usage: tools/scale_sweep.sh [tag] [steps] [workload] [extra bench flags, e.g. "--vae-parallel"]
 TAG=${1:-r06}; STEPS=${2:-3}; WL=${3:-1080p}; EXTRA=${4:-}
-OUT=gpurun_out/scale_sweep_${TAG}.jsonl
-mkdir -p gpurun_out; : > $OUT
+D=${OUT_DIR:-results}; OUT=$D/scale_sweep_${TAG}.jsonl
+mkdir -p $D; : > $OUT
 NG=$(python -c 'import torch; print(torch.cuda.device_count())')
 for N in 1 2 4 8; do
   [ "$N" -gt "$NG" ] && break
   for TR in torch rccl_direct peer_copy; do
     [ "$N" = 1 ] && [ "$TR" != torch ] && continue
     echo "== N=$N transport=$TR" >&2
-    python bench.py --gpus $N --steps $STEPS --warmup 1 --workload $WL --no-cpu-baseline --no-video-tail --transport $TR $EXTRA 2> gpurun_out/scale_sweep_${TAG}_N${N}_${TR}.err \
+    python bench.py --gpus $N --steps $STEPS --warmup 1 --workload $WL --full --no-cpu-baseline --no-video-tail --transport $TR $EXTRA 2> $D/scale_sweep_${TAG}_N${N}_${TR}.err \
       | grep '^{' | python -c "import sys, json; d = json.loads(sys.stdin.readline()); d['sweep'] = {'n': $N, 'transport_env': '$TR'}; print(json.dumps(d))" >> $OUT \
       || echo "{\"sweep\": {\"n\": $N, \"transport_env\": \"$TR\"}, \"failed\": true}" >> $OUT
   done
@@ -27,7 +27,7 @@ print(f'{"N":>2s} {"transport":12s} {"layout":28s} {"steps/s":>9s} {"s/step":>8s
 for r in rows:
     s = r['sweep']
     if r.get('failed'):
-        print(f'{s["n"]:2d} {s["transport_env"]:12s} FAILED (see gpurun_out/*.err)')
+        print(f'{s["n"]:2d} {s["transport_env"]:12s} FAILED (see the .err files beside {sys.argv[1]})')
         continue
     pf = r.get('preflight') or {}
     g = pf.get('link_gbps_measured') or {}
