@@ -384,6 +384,38 @@ int mg_image_to_u8(const float* image, int H, int W, float lo, float hi, uint8_t
  * x [T][H][W][2C] -> out [2T][H][W][C], frame 2t from channels [0,C), 2t+1 from [C,2C). */
 int mg_vae_time_interleave_f32(const float* x, int T, int64_t HW, int C, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * WanVAE encode (Encoder3d, WanVAE_.encode): the same fp32 kernels plus the pieces the decoder has no counterpart of.
+ * Pure additions to ABI 9.
+ * ---------------------------------------------------------------------------------------- */
+
+/* Convolution with a stride and one-sided padding on the same exact-f32 implicit-GEMM tile — the encoder's down-samplers
+ * (Resample downsample2d / downsample3d).  x [T][H][W][Cin], w [Cout][kt][kh][kw][Cin], out [To][Ho][Wo][Cout] with
+ * n_out = (n + pad0 + pad1 - k) / stride + 1 per axis; output (t, y, x) reads input coordinate stride * out + tap - pad0.
+ *   space: ph0 / pw0 zero rows / columns before, ph1 / pw1 behind (downsample: kh = kw = 3, stride 2, pads (0, 1));
+ *   time:  the pt0 frames before the chunk come from `cache` ([tc][H][W][Cin], its LAST frames; zeros where it has none) and
+ *          nothing is padded behind the chunk (time_conv of downsample3d: kt = 3, st = 2, pt0 = 1, tc = 1: output j reads
+ *          frames 2j-1, 2j, 2j+1 of the chunk, frame -1 being the cached one).
+ * k <= 3, strides in {1, 2}, pads < k per axis, Cin % 4 == 0; mode must be MG_VAE_EXACT (MG_ERR_ARG otherwise). */
+int mg_vae_conv_strided_f32(const float* x, const float* cache, int tc, int T, int H, int W, int Cin, const float* w, const float* bias,
+                            int Cout, int kt, int kh, int kw, int st, int sh, int sw, int pt0, int ph0, int ph1, int pw0, int pw1,
+                            float* out, int mode, void* stream);
+
+/* The encoder's input convolution, CausalConv3d(3, Cout, 3, padding = 1), on the STAGED video of mg_vae_video_in_f32:
+ * xs [T][H][W + 2][4] (channel 3 and the columns 0 and W + 1 are zero), cache [tc <= 2][H][W + 2][4] = the last staged frames of
+ * the previous chunk (may be NULL: zeros), w [Cout][3][3][3][4] (channel 3 zero), out [T][H][W][Cout].  The three kw taps of a
+ * voxel are one contiguous run of 12 floats, so the contraction is 9 runs = 108 k in 4 chunks of 32 instead of 27 taps of one
+ * chunk each; the padding only adds exact zeros.  mode must be MG_VAE_EXACT. */
+int mg_vae_conv_in3_f32(const float* xs, const float* cache, int tc, int T, int H, int W, const float* w, const float* bias, int Cout,
+                        float* out, int mode, void* stream);
+
+/* video [3][T][H][W] (reference layout), frames [t0, t0 + n) -> the staged layout above, out [n][H][W + 2][4] (16-byte aligned);
+ * and x [T][H][W][ldx] channels-last (the encoder's top-level conv1 output, mu | log_var) -> out [C][T][H][W] =
+ * (x[..][c] - mean[c]) * inv_std[c] for the first C <= ldx channels (WanVAE.encode's normalised mu). */
+int mg_vae_video_in_f32(const float* video, int T, int H, int W, int t0, int n, float* out, void* stream);
+int mg_vae_latent_out_f32(const float* x, int ldx, const float* mean, const float* inv_std, int C, int T, int H, int W, float* out,
+                          void* stream);
+
 #ifdef MG_AB_BUILD
 /* ------------------------------------------------------------------------------------------
  * A/B LIBRARY ONLY (libmoviigen_hip_ab.so, built from the same sources with -DMG_AB_BUILD; the product library

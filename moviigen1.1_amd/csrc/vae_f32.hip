@@ -1,4 +1,4 @@
-// WanVAE decode kernels, fp32-exact mode, for gfx950.
+// WanVAE decode and encode kernels, fp32-exact mode, for gfx950.
 //
 // The reference runs the whole VAE in fp32 (wan/modules/vae.py:623,658): 1.1 PFLOP of 3x3x3
 // causal convolutions at 1920x832x81.  gfx950 has an exact-f32 MFMA (v_mfma_f32_32x32x2_f32,
@@ -46,7 +46,15 @@ struct ConvArgs {
                                                      // the conv grid is Ho x Wo with Wo <= W columns, its column c reads input column xw0 + c (+ tap offset); the zero
                                                      // padding begins outside [0, W) of the INPUT, whose columns left and right of the window are the neighbours' halos;
                                                      // out / residual are compact ([.][Ho][Wo], phases: [.][2 H][2 Wo]).  Not with up2.
+    int st = 1, sh = 1, sw = 1, pt0 = 0, ph0 = 0, pw0 = 0;   // CV_G_STRIDED only: stride and leading pad per axis — voxel (t, y, x) of the OUTPUT grid [To][Ho][Wo] reads
+                                                     // input coordinate stride * out + tap - pad on each axis; taps outside [0, H) x [0, W) read zeros, frames < 0 the cache
 };
+
+// the gather of vae_conv_kernel (template parameter G)
+#define CV_G_PLAIN 0        // stride 1, 'same' padding: every decoder convolution
+#define CV_G_STRIDED 1      // the encoder's down-samplers: stride {1,2} per axis and a pad origin (ConvArgs st .. pw0)
+#define CV_G_IN3 2          // the encoder's input convolution on the staged video [T][H][W+2][4]: the three kw taps of a voxel are ONE run of 12
+                            // floats, so k runs over (dt, dy) x 12 = 108 floats in 4 chunks instead of 27 taps of one 32-wide chunk each
 
 // Output epilogue shared by both conv kernels: lane (l31, g) owns voxel row m and, per cout block nb and quad rq, the four
 // consecutive couts n = n0 + 32 nb + 8 rq + 4 g .. +3.  Bias and residual are LOADED IN BATCHES (all NB*4 float4 of a voxel
@@ -109,7 +117,7 @@ MG_DEV void cv_epilogue(const ConvArgs& a, const f32x16_t (&acc)[NB], int64_t m_
 // MB = 128-voxel sub-tiles per workgroup (1 = what runs; 2 = measurement variant, see launch_conv): with MB = 2 a wave owns
 // 2 x 32 voxels, every staged weight row and every weight fragment read feeds twice the MFMAs (non-MFMA instructions per MFMA:
 // 0.63 -> 0.44 at NB = 3, 0.56 -> 0.38 at NB = 4); the price is LDS for one workgroup per CU instead of two — and it loses.
-template <int NB, bool FAST = false, int MB = 1>
+template <int NB, bool FAST = false, int MB = 1, int G = CV_G_PLAIN>
 __global__ __launch_bounds__(CV_THREADS) void vae_conv_kernel(const ConvArgs a) {
     constexpr int BN = NB ? 32 * NB : 4;
     constexpr int NW = NB ? NB : 1;                   // weight rows a thread stages per chunk (NB = 0: threads 0-31 stage the 4 rows)
@@ -117,6 +125,7 @@ __global__ __launch_bounds__(CV_THREADS) void vae_conv_kernel(const ConvArgs a) 
     constexpr int NR = 4 * MB;                        // voxel rows a thread stages per chunk: rows (tid >> 3) + 32 i
     static_assert(NB || !FAST, "the Cout <= 4 form is exact only");
     static_assert(NB || MB == 1, "the Cout <= 4 form uses the 128-voxel tile");
+    static_assert(G == CV_G_PLAIN || (NB && !FAST && MB == 1), "the encoder's gathers run on the exact 128-voxel tile");
     __shared__ __attribute__((aligned(16))) float smem[2 * (BM + BN) * CV_LDS];
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -129,7 +138,7 @@ __global__ __launch_bounds__(CV_THREADS) void vae_conv_kernel(const ConvArgs a) 
     // (mg_vae_upconv_fold_weights_f32).  The conv grid is the INPUT grid, the tap origin is (py-1, px-1) and the result is
     // scattered to (2y+py, 2x+px): 4 instead of 9 taps per output, and the taps go through the cheap pointer path.
     const int ph = a.phases ? (int)blockIdx.z : 0;
-    const int oy = a.phases ? (ph >> 1) - 1 : -(a.kh / 2), ox = a.phases ? (ph & 1) - 1 : -(a.kw / 2);
+    const int oy = G == CV_G_STRIDED ? -a.ph0 : a.phases ? (ph >> 1) - 1 : -(a.kh / 2), ox = G == CV_G_STRIDED ? -a.pw0 : a.phases ? (ph & 1) - 1 : -(a.kw / 2);
     const float* const wbase = a.w + ph * a.w_phase_stride;
 
     // ---- gather bookkeeping: this thread stages rows (tid>>3)+32i, float4 column tid&7 -----------
@@ -144,13 +153,14 @@ __global__ __launch_bounds__(CV_THREADS) void vae_conv_kernel(const ConvArgs a) 
             const int rem = (int)(m - (int64_t)vt_[i] * hw);
             vy_[i] = rem / a.Wo;
             vx_[i] = rem - vy_[i] * a.Wo;
+            if (G == CV_G_STRIDED) { vt_[i] *= a.st; vy_[i] *= a.sh; vx_[i] *= a.sw; }      // from here on: the INPUT coordinate of tap offset 0 (+ pad)
         } else {
             vt_[i] = -1000000; vy_[i] = 0; vx_[i] = 0;
         }
     }
     const int ncc = (a.Cin + CV_BK - 1) / CV_BK;      // channel chunks per tap
     const int ntap = a.kt * a.kh * a.kw;
-    const int nchunk = ntap * ncc;
+    const int nchunk = G == CV_G_IN3 ? (a.kt * a.kh * 3 + 7) / 8 : ntap * ncc;      // CV_G_IN3: float4 per weight row = (dt, dy) runs of 3
 
     // Staging (r02).  v_mfma_f32_32x32x2_f32 runs at the fp32 VECTOR rate: VALU instructions do not hide behind it, whichever
     // wave issues them (PMC, profiles/r02c_pmc_vae_conv.txt: matrix pipe busy 66 % at full clock with 5.0 VALU + 3.1 SALU
@@ -183,9 +193,9 @@ __global__ __launch_bounds__(CV_THREADS) void vae_conv_kernel(const ConvArgs a) 
         const int valid = vt_[i] >= 0;                               // rows past M: every tap reads the zero page (never stored)
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
-            const int ti = vt_[i] + d - (a.kt - 1), yy = vy_[i] + d + oy, xx = vx_[i] + a.xw0 + d + ox;
+            const int ti = vt_[i] + d - (G == CV_G_STRIDED ? a.pt0 : a.kt - 1), yy = vy_[i] + d + oy, xx = vx_[i] + a.xw0 + d + ox;
             mk |= (unsigned)(valid & (d < a.kt) & ((ti >= 0) | (has_cache & (a.tc + ti >= 0)))) << d;
-            mk |= (unsigned)(valid & (d < a.kh) & (yy >= 0) & (yy < a.Ho)) << (3 + d);
+            mk |= (unsigned)(valid & (d < a.kh) & (yy >= 0) & (yy < (G == CV_G_STRIDED ? a.H : a.Ho))) << (3 + d);
             mk |= (unsigned)(valid & (d < a.kw) & (xx >= 0) & (xx < a.W)) << (6 + d);      // (this mask serves the paths without up2: input width = W)
         }
         vmask[i] = mk;
@@ -197,7 +207,7 @@ __global__ __launch_bounds__(CV_THREADS) void vae_conv_kernel(const ConvArgs a) 
             if ((ld_dy | ld_dx) == 0) {                              // wave-uniform: first tap of a temporal offset
 #pragma unroll
                 for (int i = 0; i < NR; ++i) {
-                    const int ti = vt_[i] + ld_dt - (a.kt - 1);
+                    const int ti = vt_[i] + ld_dt - (G == CV_G_STRIDED ? a.pt0 : a.kt - 1);
                     const int tt = max(ti >= 0 ? ti : a.tc + ti, 0);
                     const int vox = (tt * a.H + vy_[i]) * a.W + vx_[i] + a.xw0;       // only dereferenced when the row's bits are set
                     fbc[i] = (ti >= 0 ? a.x : base_neg) + (int64_t)max(vox, 0) * a.ldx;
@@ -224,6 +234,31 @@ __global__ __launch_bounds__(CV_THREADS) void vae_conv_kernel(const ConvArgs a) 
         }
     };
     auto load_chunk = [&]() __attribute__((always_inline)) {
+        if constexpr (G == CV_G_IN3) {
+            // float4 k4 of the weight row = run (dt, dy) = k4 / 3, part k4 % 3 of its 12 floats: columns vx .. vx + 2 of the padded row (a.W = W + 2:
+            // column 0 and W + 1 are the zero padding), so only time and rows need a validity test; ld_cc counts the chunks
+            const int k4 = ld_cc * 8 + ch4;
+            const bool k_ok = k4 < a.kt * a.kh * 3;                                 // the zero tail of the last chunk
+            const int tap = k4 / 3, part = k4 - 3 * tap;
+            const int dt = tap / a.kh, dy = tap - dt * a.kh;
+#pragma unroll
+            for (int i = 0; i < NR; ++i) {
+                const int ti = vt_[i] + dt - (a.kt - 1), yy = vy_[i] + dy - a.kh / 2;
+                const int ok = k_ok & (vt_[i] >= 0) & (yy >= 0) & (yy < a.H) & ((ti >= 0) | (has_cache & (a.tc + ti >= 0)));
+                const int tt = max(ti >= 0 ? ti : a.tc + ti, 0);
+                const int vox = (tt * a.H + min(max(yy, 0), a.H - 1)) * a.W + vx_[i];
+                const float* p = ok ? (ti >= 0 ? a.x : base_neg) + (int64_t)vox * 4 + part * 4 : zp[i];
+                const f32x4_t t = *(const f32x4_t*)p;
+                ra[i] = make_float4(t[0], t[1], t[2], t[3]);
+            }
+#pragma unroll
+            for (int i = 0; i < NW; ++i) {
+                const f32x4_t t = *(const f32x4_t*)(k_ok ? pw[i] + k4 * 4 : g_cv_zero_page);
+                rw[i] = make_float4(t[0], t[1], t[2], t[3]);
+            }
+            ++ld_cc;
+            return;
+        }
         if (ld_cc == 0) tap_pointers();                              // wave-uniform: first chunk of a tap
         const int c_raw = ld_cc * CV_BK + ch4 * 4;
         const bool c_ok = c_raw < a.Cin;                             // false only in the last chunk of a tap when Cin % 32 != 0
@@ -423,11 +458,11 @@ __global__ __launch_bounds__(256) void vae_ksplit_reduce_kernel(const float* __r
 
 // mode: MG_VAE_EXACT = fp32 MFMA (the reference's arithmetic), MG_VAE_BF16X3 = split-bf16 x 3 (opt-in fast mode) — an
 // argument of every call (ABI 7): two decodes on two streams or threads cannot change each other's arithmetic
-static int launch_conv(const ConvArgs& a, hipStream_t st, int mode) {
+static int launch_conv(const ConvArgs& a, hipStream_t st, int mode, int gather = CV_G_PLAIN) {
     if ((int64_t)(a.T > a.tc ? a.T : a.tc) * a.H * a.W > 0x7fffffffLL) return MG_ERR_SHAPE;   // 32-bit voxel index in the gather
     if (a.kt * a.kh * a.kw > 1 && a.Cin > 1024) return MG_ERR_SHAPE;                           // padding taps index the zero page by channel
     int nb;
-    if (a.Cout <= 4 && !a.phases && a.ksplit <= 1) nb = 0;        // the decoder head (96 -> 3): v_mfma_f32_4x4x1, exact in either mode
+    if (a.Cout <= 4 && !a.phases && a.ksplit <= 1 && gather == CV_G_PLAIN) nb = 0;        // the decoder head (96 -> 3): v_mfma_f32_4x4x1, exact in either mode
     else if (a.Cout <= 32) nb = 1;
     else if (a.Cout % 128 == 0) nb = 4;
     else if (a.Cout % 96 == 0) nb = 3;
@@ -441,13 +476,26 @@ static int launch_conv(const ConvArgs& a, hipStream_t st, int mode) {
     const int tile_flag = mode >> 8;        // bits 8-9 of `mode`: 0 / MG_VAE_TILE_128 = 128 voxels, MG_VAE_TILE_256 = 256 (measurements)
     mode &= 0xff;
     if (mode != MG_VAE_EXACT && mode != MG_VAE_BF16X3) return MG_ERR_ARG;
-    const int mbt = (tile_flag == 2 && nb >= 3 && mode == MG_VAE_EXACT && a.ksplit <= 1) ? 2 : 1;
+    if (gather != CV_G_PLAIN && (mode != MG_VAE_EXACT || a.phases || a.ksplit > 1 || a.up2 || a.xw0)) return MG_ERR_ARG;     // the encoder's gathers: exact only
+    const int mbt = (tile_flag == 2 && nb >= 3 && mode == MG_VAE_EXACT && a.ksplit <= 1 && gather == CV_G_PLAIN) ? 2 : 1;
     const int bm = CV_BM * mbt;
     const int64_t tiles_m = (a.M + bm - 1) / bm;
     if (tiles_m > 0x7fffffffLL) return MG_ERR_SHAPE;
     const dim3 grid((unsigned)tiles_m, (unsigned)((a.Cout + bn - 1) / bn), a.phases ? 4u : a.ksplit > 1 ? (unsigned)a.ksplit : 1u), block(CV_THREADS);
     if (nb == 0) {
         hipLaunchKernelGGL((vae_conv_kernel<0, false>), grid, block, 0, st, a);
+        return mg_check_launch();
+    }
+    if (gather == CV_G_STRIDED) {
+        if (nb == 1) hipLaunchKernelGGL((vae_conv_kernel<1, false, 1, CV_G_STRIDED>), grid, block, 0, st, a);
+        else if (nb == 3) hipLaunchKernelGGL((vae_conv_kernel<3, false, 1, CV_G_STRIDED>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((vae_conv_kernel<4, false, 1, CV_G_STRIDED>), grid, block, 0, st, a);
+        return mg_check_launch();
+    }
+    if (gather == CV_G_IN3) {
+        if (nb == 1) hipLaunchKernelGGL((vae_conv_kernel<1, false, 1, CV_G_IN3>), grid, block, 0, st, a);
+        else if (nb == 3) hipLaunchKernelGGL((vae_conv_kernel<3, false, 1, CV_G_IN3>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((vae_conv_kernel<4, false, 1, CV_G_IN3>), grid, block, 0, st, a);
         return mg_check_launch();
     }
     if (mode == MG_VAE_BF16X3) {
@@ -502,6 +550,44 @@ extern "C" int mg_vae_conv_cols_f32(const float* x, const float* cache, int tc, 
                                     const float* w, const float* bias, int Cout, int kt, int kh, int kw,
                                     const float* residual, float* out, int col0, int cols, int mode, void* stream) {
     return vae_conv_impl(x, cache, tc, T, H, W, Cin, w, bias, Cout, kt, kh, kw, 0, residual, out, col0, cols, mode, stream);
+}
+
+// The encoder's down-samplers (Resample downsample2d / downsample3d): a convolution with a stride and one-sided padding.  The conv grid is the OUTPUT grid
+// [To][Ho][Wo], n_out = (n + pad0 + pad1 - k) / stride + 1 per axis; in time pad0 = pt0 frames come from the cache (zeros where it has none) and nothing is
+// padded behind the chunk.
+extern "C" int mg_vae_conv_strided_f32(const float* x, const float* cache, int tc, int T, int H, int W, int Cin, const float* w, const float* bias, int Cout,
+                                       int kt, int kh, int kw, int st, int sh, int sw, int pt0, int ph0, int ph1, int pw0, int pw1, float* out, int mode,
+                                       void* stream) {
+    if (!x || !w || !out) return MG_ERR_ARG;
+    if (T <= 0 || H <= 0 || W <= 0 || Cin <= 0 || (Cin & 3) || Cout <= 0 || kt < 1 || kh < 1 || kw < 1 || kt > 3 || kh > 3 || kw > 3 ||      // 3-bit validity fields
+        st < 1 || sh < 1 || sw < 1 || st > 2 || sh > 2 || sw > 2 || pt0 < 0 || ph0 < 0 || ph1 < 0 || pw0 < 0 || pw1 < 0 || pt0 >= kt || ph0 >= kh || ph1 >= kh ||
+        pw0 >= kw || pw1 >= kw || tc < 0 || tc > 2 || (tc > 0 && !cache) || T + pt0 < kt || H + ph0 + ph1 < kh || W + pw0 + pw1 < kw)
+        return MG_ERR_SHAPE;
+    if (((uintptr_t)x & 15) || ((uintptr_t)w & 15) || ((uintptr_t)out & 15) || (cache && ((uintptr_t)cache & 15)) || (bias && ((uintptr_t)bias & 15))) return MG_ERR_SHAPE;
+    ConvArgs a;
+    a.x = x; a.cache = cache; a.tc = tc; a.T = T; a.H = H; a.W = W; a.Cin = Cin; a.ldx = Cin;
+    a.w = w; a.ldw = (int64_t)kt * kh * kw * Cin; a.bias = bias; a.Cout = Cout; a.kt = kt; a.kh = kh; a.kw = kw; a.up2 = 0;
+    a.residual = nullptr; a.out = out; a.ldo = Cout; a.out_scale = 1.f;
+    a.st = st; a.sh = sh; a.sw = sw; a.pt0 = pt0; a.ph0 = ph0; a.pw0 = pw0;
+    const int To = (T + pt0 - kt) / st + 1;
+    a.Ho = (H + ph0 + ph1 - kh) / sh + 1; a.Wo = (W + pw0 + pw1 - kw) / sw + 1; a.M = (int64_t)To * a.Ho * a.Wo;
+    return launch_conv(a, (hipStream_t)stream, mode, CV_G_STRIDED);
+}
+
+// The encoder's input convolution (CausalConv3d(3, Cout, 3, padding = 1)) on the staged video of mg_vae_video_in_f32: xs [T][H][W + 2][4] (columns 0 and W + 1
+// and channel 3 are zero), cache [tc][H][W + 2][4] = the last tc <= 2 staged frames of the previous chunk, w [Cout][3][3][3][4] (channel 3 zero: the padding
+// adds exact zeros), out [T][H][W][Cout].
+extern "C" int mg_vae_conv_in3_f32(const float* xs, const float* cache, int tc, int T, int H, int W, const float* w, const float* bias, int Cout, float* out,
+                                   int mode, void* stream) {
+    if (!xs || !w || !out) return MG_ERR_ARG;
+    if (T <= 0 || H <= 0 || W <= 0 || Cout <= 0 || tc < 0 || tc > 2 || (tc > 0 && !cache)) return MG_ERR_SHAPE;
+    if (((uintptr_t)xs & 15) || ((uintptr_t)w & 15) || ((uintptr_t)out & 15) || (cache && ((uintptr_t)cache & 15)) || (bias && ((uintptr_t)bias & 15))) return MG_ERR_SHAPE;
+    if ((int64_t)(T > tc ? T : tc) * H * ((int64_t)W + 2) > 0x7fffffffLL) return MG_ERR_SHAPE;
+    ConvArgs a;
+    a.x = xs; a.cache = cache; a.tc = tc; a.T = T; a.H = H; a.W = W + 2; a.Cin = 4; a.ldx = 4;
+    a.w = w; a.ldw = 108; a.bias = bias; a.Cout = Cout; a.kt = 3; a.kh = 3; a.kw = 3; a.up2 = 0;
+    a.residual = nullptr; a.out = out; a.ldo = Cout; a.Ho = H; a.Wo = W; a.M = (int64_t)T * H * W; a.out_scale = 1.f;
+    return launch_conv(a, (hipStream_t)stream, mode, CV_G_IN3);
 }
 
 // w [Cout][1][3][3][Cin] -> wp [4 phases = 2 py + px][Cout][2][2][Cin]: the taps of a 3x3 kernel that fall on the same image
@@ -783,6 +869,55 @@ extern "C" int mg_vae_video_out_f32(const float* x, int C, int T, int H, int W, 
     if (g > 16384) g = 16384;
     hipLaunchKernelGGL(video_out_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, x, C, T, hw, out,
                        t_off, T_total);
+    return mg_check_launch();
+}
+
+// video [3][T][H][W] (the reference layout), frames [t0, t0 + n) -> the staged layout of the input convolution: out [n][H][W + 2][4], channel 3 and the
+// columns 0 and W + 1 zero (the convolution's W padding, materialised so that the three kw taps of a voxel are one contiguous run)
+__global__ void video_in_kernel(const float* __restrict__ v, int T, int H, int W, int t0, int n, float4* __restrict__ out) {
+    const int Wp = W + 2;
+    const int64_t total = (int64_t)n * H * Wp, hw = (int64_t)H * W;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int xp = (int)(i % Wp);
+        const int64_t r = i / Wp;
+        const int y = (int)(r % H), t = (int)(r / H);
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (xp >= 1 && xp <= W) {
+            const int64_t p = ((int64_t)(t0 + t) * H + y) * W + xp - 1;
+            o.x = v[p]; o.y = v[(int64_t)T * hw + p]; o.z = v[2 * (int64_t)T * hw + p];
+        }
+        out[i] = o;
+    }
+}
+
+extern "C" int mg_vae_video_in_f32(const float* video, int T, int H, int W, int t0, int n, float* out, void* stream) {
+    if (!video || !out) return MG_ERR_ARG;
+    if (T <= 0 || H <= 0 || W <= 0 || t0 < 0 || n <= 0 || t0 + n > T || ((uintptr_t)out & 15)) return MG_ERR_SHAPE;
+    int64_t g = ((int64_t)n * H * (W + 2) + 255) / 256;
+    if (g > 16384) g = 16384;
+    hipLaunchKernelGGL(video_in_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, video, T, H, W, t0, n, (float4*)out);
+    return mg_check_launch();
+}
+
+// x [thw][ldx] channels-last (the 2 z_dim channels of the encoder's conv1: mu | log_var) -> out [C][thw], (mu - mean) * inv_std for the first C channels
+// (WanVAE_.encode; log_var is dropped)
+__global__ void latent_out_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ mean, const float* __restrict__ inv_std, int C, int64_t thw,
+                                  float* __restrict__ out) {
+    const int64_t total = thw * C;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t v = i % thw;
+        const int c = (int)(i / thw);
+        out[i] = (x[v * ldx + c] - mean[c]) * inv_std[c];
+    }
+}
+
+extern "C" int mg_vae_latent_out_f32(const float* x, int ldx, const float* mean, const float* inv_std, int C, int T, int H, int W, float* out, void* stream) {
+    if (!x || !mean || !inv_std || !out) return MG_ERR_ARG;
+    if (C <= 0 || ldx < C || T <= 0 || H <= 0 || W <= 0) return MG_ERR_SHAPE;
+    const int64_t thw = (int64_t)T * H * W;
+    int64_t g = (thw * C + 255) / 256;
+    if (g > 8192) g = 8192;
+    hipLaunchKernelGGL(latent_out_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, x, ldx, mean, inv_std, C, thw, out);
     return mg_check_launch();
 }
 

@@ -332,6 +332,73 @@ def vae_time_interleave(x, out):
     return out
 
 
+def vae_conv_strided_out_shape(x_shape, kernel, stride, pad_t0, pad_h, pad_w):
+    """[To, Ho, Wo] of vae_conv_strided: n_out = (n + pad0 + pad1 - k) // stride + 1 per axis."""
+    T, H, W = x_shape[:3]
+    (kt, kh, kw), (st, sh, sw) = kernel, stride
+    return [(T + pad_t0 - kt) // st + 1, (H + pad_h[0] + pad_h[1] - kh) // sh + 1, (W + pad_w[0] + pad_w[1] - kw) // sw + 1]
+
+
+def vae_conv_strided(x, w, bias, out, stride, pad_t0=0, pad_h=(0, 0), pad_w=(0, 0), cache=None, mode=VAE_EXACT):
+    """x [T,H,W,Cin]; w [Cout,kt,kh,kw,Cin]; out [To,Ho,Wo,Cout] (vae_conv_strided_out_shape): the encoder's down-sampling
+    convolutions — stride per axis, zero rows / columns pad_h / pad_w = (before, behind), pad_t0 frames before the chunk
+    from `cache` (its last frames)."""
+    for n, t in (('x', x), ('w', w), ('bias', bias), ('out', out), ('cache', cache)):
+        _chk(t, torch.float32, n)
+    T, H, W, Cin = x.shape
+    Cout, kt, kh, kw, wc = w.shape
+    want = vae_conv_strided_out_shape(x.shape, (kt, kh, kw), stride, pad_t0, pad_h, pad_w) + [Cout]
+    if wc != Cin or list(out.shape) != want or not out.is_contiguous() or not x.is_contiguous() or not w.is_contiguous():
+        raise lib.MoviigenHipError(f'vae_conv_strided: x {tuple(x.shape)}, w {tuple(w.shape)} need a contiguous out {want}, got {tuple(out.shape)}')
+    if cache is not None and (tuple(cache.shape[1:]) != tuple(x.shape[1:]) or not cache.is_contiguous()):
+        raise lib.MoviigenHipError('vae_conv_strided: the cache must have the frame geometry of x')
+    tc = 0 if cache is None else cache.shape[0]
+    lib.call('mg_vae_conv_strided_f32', _p(x), _p(cache), tc, T, H, W, Cin, _p(w), _p(bias), Cout, kt, kh, kw, int(stride[0]), int(stride[1]),
+             int(stride[2]), int(pad_t0), int(pad_h[0]), int(pad_h[1]), int(pad_w[0]), int(pad_w[1]), _p(out), int(mode), _st())
+    return out
+
+
+def vae_video_in(video, t0, n, out):
+    """video [3,T,H,W] fp32, frames [t0, t0 + n) -> out [n,H,W+2,4]: the staged layout of vae_conv_in3 (zero columns 0 and W+1, zero channel 3)."""
+    _chk(video, torch.float32, 'video'); _chk(out, torch.float32, 'out')
+    if video.dim() != 4 or video.shape[0] != 3 or not video.is_contiguous():
+        raise lib.MoviigenHipError('video must be a contiguous [3, T, H, W] tensor')
+    _, T, H, W = video.shape
+    if tuple(out.shape) != (n, H, W + 2, 4) or not out.is_contiguous():
+        raise lib.MoviigenHipError(f'vae_video_in: out must be a contiguous {(n, H, W + 2, 4)} tensor, got {tuple(out.shape)}')
+    lib.call('mg_vae_video_in_f32', _p(video), T, H, W, int(t0), int(n), _p(out), _st())
+    return out
+
+
+def vae_conv_in3(xs, w, bias, out, cache=None, mode=VAE_EXACT):
+    """the 3 -> Cout causal 3x3x3 input convolution: xs [T,H,W+2,4] from vae_video_in, cache [<= 2,H,W+2,4] staged frames of the
+    previous chunk, w [Cout,3,3,3,4] (channel 3 zero), out [T,H,W,Cout]."""
+    for n, t in (('xs', xs), ('w', w), ('bias', bias), ('out', out), ('cache', cache)):
+        _chk(t, torch.float32, n)
+    T, H, Wp, c4 = xs.shape
+    Cout = w.shape[0]
+    if c4 != 4 or tuple(w.shape) != (Cout, 3, 3, 3, 4) or tuple(out.shape) != (T, H, Wp - 2, Cout) or not (xs.is_contiguous() and w.is_contiguous()
+                                                                                                     and out.is_contiguous()):
+        raise lib.MoviigenHipError(f'vae_conv_in3: xs {tuple(xs.shape)}, w {tuple(w.shape)}, out {tuple(out.shape)}')
+    if cache is not None and (tuple(cache.shape[1:]) != tuple(xs.shape[1:]) or not cache.is_contiguous()):
+        raise lib.MoviigenHipError('vae_conv_in3: the cache must have the staged frame geometry of xs')
+    tc = 0 if cache is None else cache.shape[0]
+    lib.call('mg_vae_conv_in3_f32', _p(xs), _p(cache), tc, T, H, Wp - 2, _p(w), _p(bias), Cout, _p(out), int(mode), _st())
+    return out
+
+
+def vae_latent_out(x, mean, inv_std, out):
+    """x [T,H,W,Cx] channels-last -> out [C,T,H,W] = (x[..., :C] - mean) * inv_std (C = out.shape[0] <= Cx)."""
+    for n, t in (('x', x), ('mean', mean), ('inv_std', inv_std), ('out', out)):
+        _chk(t, torch.float32, n)
+    T, H, W, Cx = x.shape
+    C = out.shape[0]
+    if tuple(out.shape) != (C, T, H, W) or C > Cx or mean.numel() < C or inv_std.numel() < C or not (x.is_contiguous() and out.is_contiguous()):
+        raise lib.MoviigenHipError(f'vae_latent_out: x {tuple(x.shape)}, out {tuple(out.shape)}')
+    lib.call('mg_vae_latent_out_f32', _p(x), Cx, _p(mean), _p(inv_std), C, T, H, W, _p(out), _st())
+    return out
+
+
 def video_to_u8(video, lo=-1.0, hi=1.0):
     """[3,T,H,W] fp32 -> uint8 frames [T,H,W,3] (reference cache_video arithmetic)."""
     _chk(video, torch.float32, 'video')

@@ -1,10 +1,10 @@
-"""WanVAE decode on MI355X — drop-in for the decode side of reference wan/modules/vae.py.
+"""WanVAE on MI355X — drop-in for reference wan/modules/vae.py, decode and encode.
 
 Public surface kept: `WanVAE(z_dim=16, vae_pth=..., dtype=torch.float, device=...)`,
 `.model.z_dim`, `.decode(list[Tensor[16,T,h,w]]) -> list[Tensor[3,4T-3,8h,8w]]` fp32 in [-1,1]
-(reference vae.py:619-663), reading the reference checkpoint `Wan2.1_VAE.pth` (a plain
-state_dict; encoder tensors are ignored: VAE *encode* is training-side preprocessing, out of the
-denoising hot path).
+(reference vae.py:619-663) and `.encode(list[Tensor[3,T,H,W]]) -> list[Tensor[16,1+(T-1)//4,H//8,W//8]]` fp32 (the
+normalised mu), reading the reference checkpoint `Wan2.1_VAE.pth` (a plain state_dict).  A state dict without the
+encoder tensors still constructs and decodes; `encode` on it raises a ValueError naming the missing keys.
 
 Execution: activations are channels-last [T][H][W][C] fp32 on the device; every convolution
 (3x3x3 causal, 3x1x1 time_conv, 3x3 after nearest-2x, 1x1) is ONE implicit-GEMM launch on the
@@ -12,6 +12,14 @@ exact-f32 MFMA (mg_vae_conv_f32) with the causal cache, the zero padding, the 2x
 bias and the residual add folded in; RMS_norm+SiLU and the per-frame d=384 attention are HIP
 kernels as well.  The chunked decode with its 2-frame feature cache follows the reference
 protocol (vae.py:101-141,202-220,423-472,544-568) slot for slot.
+
+The encoder (Encoder3d, WanVAE_.encode) reuses all of that and adds what the decoder has no counterpart of: the
+down-samplers' 3x3 convolution of stride 2 behind a one-sided zero pad and their 3x1x1 temporal convolution of stride 2
+with a one-frame cache (mg_vae_conv_strided_f32: the same tile with a strided gather), the 3 -> dim input convolution on
+a [T][H][W+2][4] staging of the chunk's frames (mg_vae_conv_in3_f32: 108 k in 4 chunks instead of 27 taps) and the
+layout kernels at both ends.  Chunks are the reference's: frame 0, then groups of four.  0.67 PFLOP for a 1920x832x81
+clip: 5.82 s (0.73 of the fp32-MFMA peak; the decode: 8.9 s, 0.76), peak device memory 18.4 GB including the 1.55 GB clip
+(the decode: 45 GB) — profiles/vae_encode_bench.log.
 """
 import logging
 import os
@@ -92,8 +100,8 @@ class _Band:
 
 
 class WanVAE_:
-    """decoder-side container: parameters keyed by the reference state_dict names, repacked for
-    the channels-last kernels ([Cout,Cin,kt,kh,kw] -> [Cout,kt,kh,kw,Cin])."""
+    """container of both halves: parameters keyed by the reference state_dict names (decoder.*, conv2.*; encoder.*, conv1.* when the
+    state dict has them), repacked for the channels-last kernels ([Cout,Cin,kt,kh,kw] -> [Cout,kt,kh,kw,Cin])."""
 
     def __init__(self, state_dict, z_dim=16, device='cuda', upconv='phases', mode='exact', tile='auto'):
         """upconv: how the 3x3 conv behind a nearest-2x upsample runs — 'phases' = four 2x2 convs of the image with
@@ -114,9 +122,11 @@ class WanVAE_:
         self.device = torch.device(device)
         self.P = {}
         for k, v in state_dict.items():
-            if not (k.startswith('decoder.') or k.startswith('conv2.')):
+            if not k.startswith(('decoder.', 'conv2.', 'encoder.', 'conv1.')):
                 continue
             v = v.to(torch.float32)
+            if k == 'encoder.conv1.weight':                  # [Cout,3,3,3,3]: a zero fourth input channel for the staged video (ops.vae_conv_in3)
+                v = torch.nn.functional.pad(v, (0, 0, 0, 0, 0, 0, 0, 4 - v.shape[1]))
             if k.endswith('weight') and v.dim() == 5:
                 v = v.permute(0, 2, 3, 4, 1)
             elif k.endswith('weight') and v.dim() == 4:      # Conv2d -> kt = 1
@@ -135,6 +145,13 @@ class WanVAE_:
         self.mean = torch.tensor(_MEAN[:z_dim], dtype=torch.float32, device=self.device)
         self.inv_std = (1.0 / torch.tensor(_STD[:z_dim], dtype=torch.float32)).to(self.device)
         self._band = None                  # set for the duration of a decode_spatial call: this rank's column band
+        # the encoder half, when the state dict has it (n_slots, layout and _stages() above are decoder quantities)
+        n_down = 1 + max([int(k.split('.')[2]) for k in self.P if k.startswith('encoder.downsamples.')], default=-1)
+        self.enc_layout = []
+        for i in range(n_down):
+            pre = f'encoder.downsamples.{i}.'
+            self.enc_layout.append(('down' if (pre + 'resample.1.weight') in self.P else 'res', pre))
+        self.enc_missing = [k for k in _ENCODER_KEYS if k not in self.P]
 
     # ---- building blocks -----------------------------------------------------------------------
     def _new(self, *shape):
@@ -238,6 +255,71 @@ class WanVAE_:
             self._band.scale *= 2
             return ops.vae_upconv_phases_cols(xh, wp, self.P[name + '.bias'], self._new(T, 2 * H, 2 * W, wp.shape[1]), col0, mode=self._conv_mode)
         return ops.vae_upconv_phases(x, wp, self.P[name + '.bias'], self._new(T, 2 * H, 2 * W, wp.shape[1]), mode=self._conv_mode)
+
+    # ---- the encoder (reference Encoder3d.forward, Resample downsample2d / downsample3d, WanVAE_.encode) ----------------
+    def _down(self, pre, x, cache, idx):
+        """Resample, down-sampling: per frame a 3x3 convolution of stride 2 behind a zero pad of (0 before, 1 behind) on H and W; downsample3d then
+        a 3x1x1 convolution of stride 2 in time over [last frame of the previous chunk | the chunk], no temporal padding — the first chunk (one
+        frame) passes through and is remembered."""
+        name = pre + 'resample.1'
+        w = self.P[name + '.weight']
+        shp = ops.vae_conv_strided_out_shape(x.shape, (1, 3, 3), (1, 2, 2), 0, (0, 1), (0, 1))
+        y = ops.vae_conv_strided(x, w, self.P[name + '.bias'], self._new(*shp, w.shape[0]), (1, 2, 2), 0, (0, 1), (0, 1), mode=self._conv_mode & 0xff)
+        if (pre + 'time_conv.weight') in self.P:
+            i = idx[0]
+            keep = y[-1:].clone()
+            if cache[i] is not None:
+                wt = self.P[pre + 'time_conv.weight']
+                shp = ops.vae_conv_strided_out_shape(y.shape, (3, 1, 1), (2, 1, 1), 1, (0, 0), (0, 0))
+                y = ops.vae_conv_strided(y, wt, self.P[pre + 'time_conv.bias'], self._new(*shp, wt.shape[0]), (2, 1, 1), 1, cache=cache[i],
+                                         mode=self._conv_mode & 0xff)
+            cache[i] = keep
+            idx[0] += 1
+        return y
+
+    def _encoder_chunk(self, video, t0, n, cache):
+        """Encoder3d.forward on the frames [t0, t0 + n) of video [3,T,H,W] -> [n', H/8, W/8, 2 z_dim] channels-last."""
+        _, _, H, W = video.shape
+        xs = ops.vae_video_in(video, t0, n, self._new(n, H, W + 2, 4))          # only the chunk is ever staged
+        prev = cache[0]                                                        # the feat_cache protocol of _cached_conv, on staged frames
+        if n >= CACHE_T:
+            cx = xs[-CACHE_T:].clone()
+        elif prev is not None:
+            cx = torch.cat([prev[-1:], xs[-1:]], dim=0)
+        else:
+            cx = xs[-1:].clone()
+        w = self.P['encoder.conv1.weight']
+        x = ops.vae_conv_in3(xs, w, self.P['encoder.conv1.bias'], self._new(n, H, W, w.shape[0]), cache=prev, mode=self._conv_mode & 0xff)
+        cache[0] = cx
+        del xs, prev
+        idx = [1]
+        for kind, pre in self.enc_layout:
+            x = self._res(pre, x, cache, idx) if kind == 'res' else self._down(pre, x, cache, idx)
+        x = self._res('encoder.middle.0.', x, cache, idx)
+        x = self._attn('encoder.middle.1.', x)
+        x = self._res('encoder.middle.2.', x, cache, idx)
+        x = self._norm_silu(x, 'encoder.head.0.gamma')
+        return self._cached_conv('encoder.head.2', x, cache, idx)
+
+    @torch.no_grad()
+    def encode(self, x):
+        """x [3,T,H,W] (fp32 or castable; T >= 1, H, W >= 8) -> the normalised mu [z_dim, 1 + (T-1)//4, H//8, W//8] fp32 on the model's device.
+        Chunk 0 is frame 0 alone, chunk i >= 1 the frames 1 + 4(i-1) .. 4i with the encoder's causal caches carried over (the chunking is fixed
+        by the temporal stride: there is nothing to choose); frames behind the last full group of four are not read, as in the reference."""
+        if self.enc_missing:
+            raise ValueError('encode needs the encoder half of the checkpoint; the state dict has no ' + ', '.join(self.enc_missing))
+        if self.mode != 'exact':
+            raise ValueError("encode runs in the reference's fp32 arithmetic only (mode='exact'): the strided and the input convolution have no bf16x3 form")
+        if not torch.is_tensor(x) or x.dim() != 4 or x.shape[0] != 3 or x.shape[1] < 1 or x.shape[2] < 8 or x.shape[3] < 8:
+            raise ValueError(f'encode expects a video tensor [3, T >= 1, H >= 8, W >= 8], got {tuple(x.shape) if torch.is_tensor(x) else type(x)}')
+        x = x.to(self.device, torch.float32).contiguous()
+        T = x.shape[1]
+        cache = [None] * (sum(1 for k, v in self.P.items() if k.startswith('encoder.') and k.endswith('weight') and v.dim() == 5) + 8)
+        outs = []
+        for i in range(1 + (T - 1) // 4):
+            outs.append(self._encoder_chunk(x, 0, 1, cache) if i == 0 else self._encoder_chunk(x, 1 + 4 * (i - 1), 4, cache))
+        y = self._conv('conv1', torch.cat(outs, dim=0) if len(outs) > 1 else outs[0])           # [T', h, w, 2 z_dim]: mu | log_var
+        return ops.vae_latent_out(y, self.mean, self.inv_std, self._new(self.z_dim, *y.shape[:3]))
 
     # ---- the decoder as a list of stages (each owns a contiguous range of feat_cache slots) ---------
     def _stages(self):
@@ -492,6 +574,12 @@ class WanVAE_:
         return video
 
 
+# what `encode` reads besides the decoder's tensors; the per-level modules follow from the key names (WanVAE_.enc_layout)
+_ENCODER_KEYS = ('encoder.conv1.weight', 'encoder.conv1.bias', 'encoder.downsamples.0.residual.2.weight', 'encoder.middle.0.residual.2.weight',
+                 'encoder.middle.1.to_qkv.weight', 'encoder.middle.1.proj.weight', 'encoder.middle.2.residual.2.weight', 'encoder.head.0.gamma',
+                 'encoder.head.2.weight', 'encoder.head.2.bias', 'conv1.weight', 'conv1.bias')
+
+
 # measured cost per multiply-add of the decoder's kernel classes, relative to the 384- / 192-channel 3x3x3 convolutions
 # (vae_conv_kernel<4>), 1920x832 latent, 4-frame chunks — profiles/r04*_vae_stages.txt, tools/bench_vae.py --stages:
 #   narrow = the 96-channel stage (vae_conv_kernel<3>: three of four MFMA column blocks of a 128-wide tile),
@@ -560,8 +648,8 @@ class WanVAE:
         self.scale = [self.mean, 1.0 / self.std]
 
     def encode(self, videos):
-        raise NotImplementedError('VAE encode is training-side preprocessing (reference '
-                                  'scripts/data_preprocess), outside the denoising hot path')
+        """videos: list of [3,T,H,W] -> list of normalised mu latents [16, 1 + (T-1)//4, H//8, W//8] fp32 (reference WanVAE.encode)."""
+        return [self.model.encode(u) for u in videos]
 
     def decode(self, zs):
         return [self.model.decode(u) for u in zs]

@@ -1,6 +1,10 @@
 """Time WanVAE decode (BASELINE.json configs[4]: 1920x832x81f latent -> pixels) on one MI355X.
     python tools/bench_vae.py [--size 1920x832] [--frames 81] [--chunk N]
-Synthetic weights of the shipped decoder shape (dim 96), z = randn seed 7."""
+Synthetic weights of the shipped decoder shape (dim 96), z = randn seed 7.
+    python tools/bench_vae.py --chunk 4 --encode [--stages]
+also times WanVAE.encode of a [3,81,832,1920] and a [3,81,720,1280] clip (median of --encode-reps calls, events around the whole
+call) behind the decode leg of the same run: seconds, executed TFLOP/s against the same fp32-MFMA peak, peak memory; with --stages
+the milliseconds and TFLOP/s of every encoder stage."""
 import argparse
 import json
 import os
@@ -27,11 +31,18 @@ ap.add_argument('--bands', type=int, nargs='*', default=[], metavar='P',
                      'rank + the bytes it would put on a link, priced at --link-gbps.  Lines are marked `invalid: emulation`')
 ap.add_argument('--link-gbps', type=float, default=45.0)
 ap.add_argument('--upconv', default='phases', choices=('phases', 'gather'), help="the convs behind a 2x upsample: four 2x2 phase convs / one 3x3 through the upsample")
+ap.add_argument('--encode', action='store_true', help='after the decode leg: time WanVAE.encode at 1920x832x81 and 1280x720x81 (random dim-96 encoder weights)')
+ap.add_argument('--encode-reps', type=int, default=3)
 args = ap.parse_args()
 Wd, Hd = (int(v) for v in args.size.split('x'))
 T = (args.frames - 1) // 4 + 1
 dev = torch.device('cuda:0')
-vae = wan.modules.WanVAE(state_dict=W.make_vae_params(96, 1), device=dev, upconv=args.upconv, mode=args.mode,
+params = W.make_vae_params(96, 1)
+if args.encode:
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    from vae_encode_ref import make_vae_encoder_params
+    params.update(make_vae_encoder_params(96, 2))            # (the decode does not read them: tests/test_vae_encode.py)
+vae = wan.modules.WanVAE(state_dict=params, device=dev, upconv=args.upconv, mode=args.mode,
                          tile=args.tile if args.tile == 'auto' else int(args.tile))
 z = torch.randn(16, T, Hd // 8, Wd // 8, generator=torch.Generator().manual_seed(7)).to(dev)
 chunks = [1] + [args.chunk] * ((T - 1) // args.chunk) + ([(T - 1) % args.chunk] if (T - 1) % args.chunk else [])
@@ -51,6 +62,64 @@ flops = (1065.8e12 if args.upconv == 'phases' else 1116.5e12) * (Wd * Hd * args.
 print(json.dumps({'metric': 'vae_decode_sec', 'value': dt, 'second_decode_sec': dt_warm, 'upconv': args.upconv, 'mode': args.mode, 'tile': args.tile, 'size': args.size, 'frames': args.frames, 'chunks': chunks[:3],
                   'tflops_fp32': flops / dt / 1e12, 'fp32_mfma_peak_tflops': 157.3, 'frac': flops / dt / 157.3e12,
                   'finite': bool(torch.isfinite(video).all().item()), 'peak_mem_gb': torch.cuda.max_memory_allocated() / 2**30}))
+
+if args.encode:
+    sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    from vae_flops import vae_encode_flops, vae_encode_stage_flops
+    decode_frac = flops / min(dt, dt_warm) / 157.3e12
+    del video
+    m = vae.model
+    vae.encode([torch.rand(3, 5, 64, 64, device=dev)])        # warm-up: every kernel loaded
+    for (eh, ew) in ((832, 1920), (720, 1280)):
+        clip = torch.rand(3, 81, eh, ew, device=dev, generator=torch.Generator(device=dev).manual_seed(9)) * 2 - 1
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base_mem = torch.cuda.memory_allocated()
+        secs = []
+        for _ in range(max(3, args.encode_reps)):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            lat = vae.encode([clip])[0]
+            b.record()
+            torch.cuda.synchronize()
+            secs.append(a.elapsed_time(b) / 1e3)
+        med = sorted(secs)[len(secs) // 2]
+        ef = vae_encode_flops(81, eh, ew)
+        print(json.dumps({'metric': 'vae_encode_sec', 'value': med, 'all_sec': secs, 'size': f'{ew}x{eh}', 'frames': 81, 'latent': list(lat.shape),
+                          'pflop': ef / 1e15, 'tflops_fp32': ef / med / 1e12, 'fp32_mfma_peak_tflops': 157.3, 'frac': ef / med / 157.3e12,
+                          'decode_frac_same_run': decode_frac, 'finite': bool(torch.isfinite(lat).all().item()),
+                          'peak_mem_gb': torch.cuda.max_memory_allocated() / 2**30, 'of_which_clip_and_weights_gb': base_mem / 2**30}))
+        if args.stages:
+            acc, order = {}, []
+
+            def wrap(fn, key_of):
+                def timed(*a_, **k_):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    y = fn(*a_, **k_)
+                    e1.record()
+                    key = key_of(*a_, **k_)
+                    if key not in acc:
+                        order.append(key)
+                    acc.setdefault(key, []).append((e0, e1))
+                    return y
+                return timed
+            o_res, o_down, o_attn, o_chunk = m._res, m._down, m._attn, m._encoder_chunk
+            m._res, m._down, m._attn = wrap(o_res, lambda pre, *r: pre), wrap(o_down, lambda pre, *r: pre), wrap(o_attn, lambda pre, *r: pre)
+            m._encoder_chunk = wrap(o_chunk, lambda *r: 'chunk')
+            vae.encode([clip])
+            torch.cuda.synchronize()
+            m._res, m._down, m._attn, m._encoder_chunk = o_res, o_down, o_attn, o_chunk
+            ms = {k: sum(x.elapsed_time(y) for x, y in v) for k, v in acc.items()}
+            sf = vae_encode_stage_flops(81, eh, ew)
+            rest = ms.pop('chunk') - sum(ms.values())               # video_in + encoder.conv1 + head (norm, conv) of every chunk
+            print(f'encode {ew}x{eh}x81 stage                 total_ms   TFLOP   TFLOP/s   frac_of_peak')
+            for k in [k for k in order if k != 'chunk']:
+                print(f'{k:40s} {ms[k]:9.1f} {sf[k] / 1e12:7.1f} {sf[k] / ms[k] / 1e9:9.1f} {sf[k] / ms[k] / 1e9 / 157.3:10.2f}')
+            fr = sf['encoder.conv1'] + sf['encoder.head']
+            print(f"{'video_in + encoder.conv1 + encoder.head':40s} {rest:9.1f} {fr / 1e12:7.1f} {fr / rest / 1e9:9.1f} {fr / rest / 1e9 / 157.3:10.2f}")
+        del clip, lat
 
 if args.bands:
     # one rank of P, emulated: what the W split costs a rank in kernels and copies (measured) and in link time (bytes / rate, not overlapped)
