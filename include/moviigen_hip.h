@@ -103,6 +103,29 @@ int mg_gemm_bf16(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw,
                  const float* bias, int64_t M, int N, int K, int epilogue, void* out,
                  int64_t ldo, const float* gate, void* stream);
 
+/* MXFP8 — the opt-in arithmetic of the six per-block DiT linears (WanModel.set_gemm_precision('mxfp8'); never the default).
+ * Format: OCP MXFP8 (E4M3).  Along K every 32 consecutive elements share one E8M0 scale byte s, meaning 2^(s-127); elements
+ * are OCP e4m3fn (not the MI300 fnuz encoding).  A block with maximum magnitude amax takes e = floor(log2(amax)) - 8 clamped
+ * to [-127, 127] (a block of zeros: e = -127), scale byte e + 127, and each element is x * 2^-e, clamped to +-448 FIRST and
+ * then rounded to nearest-even into e4m3: it saturates (500 -> 448) where torch's CPU cast returns NaN.  A dequantised
+ * element, e4m3 * 2^e, is exactly a bf16 value.  The input must be finite: the format has no code for infinity, and what a NaN
+ * or an infinite element turns into (and what it does to its block's scale) is not defined.
+ *
+ * mg_quant_mxfp8_rows: x bf16 [rows][K] (row stride ldx elements) -> q e4m3 bytes [rows][K] (row stride ldq) and scale bytes
+ * [rows][K/32] (row stride lds).  Serves activations (per call) and weights ([N][K], once).  K % 128 == 0, ldx % 8 == 0,
+ * ldq % 16 == 0, lds % 4 == 0, x / q 16-byte and scales 4-byte aligned, else MG_ERR_SHAPE. */
+int mg_quant_mxfp8_rows(const uint16_t* x, int64_t ldx, int64_t rows, int K, uint8_t* q, int64_t ldq,
+                        uint8_t* scales, int64_t lds, void* stream);
+
+/* out[M][N] = A[M][K] . W[N][K]^T on the block-scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4, e4m3 operands, fp32
+ * accumulation); Aq / Wq and As / Ws are the element and scale bytes mg_quant_mxfp8_rows writes.  bias, epilogue, out, ldo
+ * and gate mean exactly what they mean in mg_gemm_bf16 (MG_EPI_*).  M arbitrary, N % 16 == 0, K % 128 == 0, lda / ldw % 16
+ * == 0, ldas / ldws % 4 == 0, ldo % 4 == 0, Aq / Wq / out 16-byte and As / Ws 4-byte aligned, else MG_ERR_SHAPE.  One
+ * workgroup per output tile, k ascending, no atomics: the result does not depend on the launch. */
+int mg_gemm_mxfp8(const uint8_t* Aq, int64_t lda, const uint8_t* As, int64_t ldas, const uint8_t* Wq, int64_t ldw,
+                  const uint8_t* Ws, int64_t ldws, const float* bias, int64_t M, int N, int K, int epilogue,
+                  void* out, int64_t ldo, const float* gate, void* stream);
+
 /* softmax(q k^T * scale) v, non-causal, keys >= Lk masked; bf16 in/out, fp32 accumulate,
  * head_dim 128.  Replaces flash_attn_varlen_func as called from
  * wan/modules/attention.py:96-127 (self-attention model.py:146-151, k_lens=seq_lens;

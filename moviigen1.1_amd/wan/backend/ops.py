@@ -84,6 +84,42 @@ def gemm(a, w, bias, epilogue, out, gate=None):
     return out
 
 
+def quant_mxfp8(x, q=None, scales=None):
+    """x [rows, K] bf16 (row stride free) -> (q uint8 [rows, K] e4m3fn bytes, scales uint8 [rows, K/32] E8M0 bytes): OCP MXFP8
+    with the project's saturating definition (include/moviigen_hip.h).  q / scales are allocated when not given."""
+    _chk(x, torch.bfloat16, 'x')
+    if x.dim() != 2:
+        raise lib.MoviigenHipError(f'quant_mxfp8: expected [rows, K], got {tuple(x.shape)}')
+    rows, K = x.shape
+    if q is None:
+        q = torch.empty(rows, K, dtype=torch.uint8, device=x.device)
+    if scales is None:
+        scales = torch.empty(rows, K // 32, dtype=torch.uint8, device=x.device)
+    _chk(q, torch.uint8, 'q'); _chk(scales, torch.uint8, 'scales')
+    if tuple(q.shape) != (rows, K) or tuple(scales.shape) != (rows, K // 32):
+        raise lib.MoviigenHipError(f'quant_mxfp8 shape mismatch x{tuple(x.shape)} q{tuple(q.shape)} scales{tuple(scales.shape)}')
+    lib.call('mg_quant_mxfp8_rows', _p(x), x.stride(0), rows, K, _p(q), q.stride(0), _p(scales), scales.stride(0), _st())
+    return q, scales
+
+
+def gemm_mxfp8(aq, a_scales, wq, w_scales, bias, epilogue, out, gate=None):
+    """out[M,N] (+)= dequant(aq, a_scales)[M,K] @ dequant(wq, w_scales)[N,K]^T (+bias ...) on the block-scaled MFMA; the epilogues
+    of `gemm` (MG_EPI_* in include/moviigen_hip.h)."""
+    _chk(aq, torch.uint8, 'aq'); _chk(a_scales, torch.uint8, 'a_scales'); _chk(wq, torch.uint8, 'wq')
+    _chk(w_scales, torch.uint8, 'w_scales'); _chk(bias, torch.float32, 'bias'); _chk(gate, torch.float32, 'gate')
+    want = torch.bfloat16 if epilogue in (BIAS_BF16, BIAS_GELU_BF16) else torch.float32
+    _chk(out, want, 'out')
+    M, K = aq.shape
+    N = wq.shape[0]
+    if (wq.shape[1] != K or out.shape[0] != M or out.shape[1] != N or tuple(a_scales.shape) != (M, K // 32)
+            or tuple(w_scales.shape) != (N, K // 32)):
+        raise lib.MoviigenHipError(f'gemm_mxfp8 shape mismatch aq{tuple(aq.shape)} a_scales{tuple(a_scales.shape)} '
+                                   f'wq{tuple(wq.shape)} w_scales{tuple(w_scales.shape)} out{tuple(out.shape)}')
+    lib.call('mg_gemm_mxfp8', _p(aq), aq.stride(0), _p(a_scales), a_scales.stride(0), _p(wq), wq.stride(0), _p(w_scales),
+             w_scales.stride(0), _p(bias), M, N, K, int(epilogue), _p(out), out.stride(0), _p(gate), _st())
+    return out
+
+
 _ATTN_WS = {}
 
 

@@ -191,6 +191,19 @@ def rope_cos_sin(head_dim, grid, theta=10000.0):
     return torch.from_numpy(np.concatenate(parts).astype(np.float32))
 
 
+# set_gemm_precision('mxfp8'): which of the six per-block linears run on mg_gemm_mxfp8.  A site is True only if activation
+# quantisation + the MXFP8 GEMM is faster than mg_gemm_bf16 at its step shape (M = 131 040) in
+# profiles/pr_gemm_mxfp8_shapes_131040.log (tools/bench_gemm_mxfp8.py; the three fp8 sites win by 2-3 % only); a site that loses there stays bf16 in 'mxfp8' mode too.
+#   site            N      K      epilogue     bf16 ms   quantise + mxfp8 ms
+#   wqkv            15360   5120  bias         13.79     13.49   fp8
+#   self_attn.o      5120   5120  gate-resid    4.97      5.30   bf16  (cross_attn.q — the same shape, bias epilogue — and cross_attn.o too:
+#                                                                       the GEMM alone gains 0.08 ms, the quantiser costs 0.39)
+#   ffn.0           13824   5120  GELU         12.68     12.29   fp8
+#   ffn.2            5120  13824  gate-resid   12.47     12.21   fp8
+MXFP8_SITES = {'wqkv': True, 'self_attn.o': False, 'cross_attn.q': False, 'cross_attn.o': False, 'ffn.0': True, 'ffn.2': True}
+GEMM_PRECISIONS = ('bf16', 'mxfp8')
+
+
 class WanModel(nn.Module):
     ignore_for_config = ['patch_size', 'cross_attn_norm', 'qk_norm', 'text_dim', 'window_size']
     _no_split_modules = ['WanAttentionBlock']
@@ -233,6 +246,8 @@ class WanModel(nn.Module):
         # ranks, ring attention across the `ring_size` groups; None = derive from sp_size / ring
         self.uly_group, self.uly_size, self.ring_group, self.ring_size, self.ring_rank = None, None, None, None, 0
         self._packed = None
+        self.gemm_precision = 'bf16'    # set_gemm_precision: 'mxfp8' = the six per-block linears on the block-scaled MFMA (opt-in)
+        self._mx = None                 # their quantised weights, built once per set of weights
         self._ws = {}
         self._rope = {}
         self._ctx_cache = {}
@@ -312,6 +327,7 @@ class WanModel(nn.Module):
 
     def _invalidate(self):
         self._packed = None
+        self._mx = None
         self._ctx_cache = {}
 
     def _apply(self, fn, recurse=True):
@@ -355,6 +371,39 @@ class WanModel(nn.Module):
         pk['patch_w'] = self.patch_embedding.weight.data.reshape(self.dim, -1)
         self._packed = pk
         return pk
+
+    def set_gemm_precision(self, precision):
+        """Arithmetic of the six per-block linears of the layer loop (q|k|v, self_attn.o, cross_attn.q, cross_attn.o, ffn.0, ffn.2):
+        'bf16' (default, the reference's) or 'mxfp8' — OCP MXFP8 operands (e4m3 elements, one power-of-two scale per 32 along K;
+        include/moviigen_hip.h) on the block-scaled MFMA, fp32 accumulation, the same epilogues.  NOT the reference's arithmetic:
+        an opt-in like WanVAE(mode='bf16x3'), never the default, with its own parity statement.  The weights are
+        quantised once, at the next forward; the bf16 parameters stay (state_dict, and 'bf16' switches back bit for bit).  The
+        embeddings, the once-per-prompt cross k|v and the head are not touched."""
+        if precision not in GEMM_PRECISIONS:
+            raise ValueError(f'gemm precision must be one of {GEMM_PRECISIONS}, got {precision!r}')
+        if precision == 'mxfp8' and getattr(self, '_shards', None) is not None:
+            raise NotImplementedError("set_gemm_precision('mxfp8') needs resident weights: block-sharded weights (wan.distributed.fsdp) "
+                                      'are gathered in bf16 per block and are not quantised')
+        self.gemm_precision = precision
+        return self
+
+    def _mx_layers(self):
+        """per block {site: (e4m3 bytes [N, K], scale bytes [N, K/32])} for the sites MXFP8_SITES enables"""
+        if getattr(self, '_shards', None) is not None:
+            raise NotImplementedError("gemm precision 'mxfp8' does not support block-sharded weights (wan.distributed.fsdp)")
+        if self._mx is None:
+            self._mx = [{site: ops.quant_mxfp8(lw[site]) for site, on in MXFP8_SITES.items() if on}
+                        for lw in self._pack()['layers']]
+        return self._mx
+
+    def _linear(self, site, a, act, lw, mx, bias, epilogue, out, gate=None):
+        """one of the six per-block linears: mg_gemm_bf16, or (mxfp8 mode, site enabled) quantise the activation into the
+        workspace and run mg_gemm_mxfp8.  `act` names the activation's quantised buffers in the workspace."""
+        if mx is None or site not in mx:
+            return ops.gemm(a, lw[site], bias, epilogue, out, gate=gate)
+        aq, a_s = act
+        ops.quant_mxfp8(a, aq, a_s)
+        return ops.gemm_mxfp8(aq, a_s, mx[site][0], mx[site][1], bias, epilogue, out, gate=gate)
 
     def _layer(self, i):
         """GEMM operands of block i: resident, or (block-sharded mode, wan.distributed.fsdp) views of
@@ -402,6 +451,12 @@ class WanModel(nn.Module):
                 ws['part'], ws['acc'] = e(Lg, n_loc * hd), e(Lg, n_loc * hd, dt=f32)
                 ws['lse'], ws['lse_acc'] = e(n_loc, Lg, dt=f32), e(n_loc, Lg, dt=f32)
             self._ws = {key: ws}  # one live shape at a time (activations are GBs at 14B/720p)
+        if self.gemm_precision == 'mxfp8' and 'hq' not in ws:
+            # quantised activations, added to the live workspace the first time the mode runs at this shape (a model switched between
+            # the modes keeps ONE workspace): h / a share one [L, dim] pair, u has its own
+            d, f, u8 = self.dim, self.ffn_dim, torch.uint8
+            ws['hq'], ws['hs'] = torch.empty(L, d, dtype=u8, device=dev), torch.empty(L, d // 32, dtype=u8, device=dev)
+            ws['uq'], ws['us'] = torch.empty(L, f, dtype=u8, device=dev), torch.empty(L, f // 32, dtype=u8, device=dev)
         return ws
 
     def _rope_tab(self, grid, dev):
@@ -608,8 +663,11 @@ class WanModel(nn.Module):
         rope = self._rope_tab(grid, dev)
         mod = ws['mod']
 
+        mxl = self._mx_layers() if self.gemm_precision == 'mxfp8' else None
+        qd, qf = (ws.get('hq'), ws.get('hs')), (ws.get('uq'), ws.get('us'))      # quantised [L, dim] / [L, ffn_dim] activation
         for i, blk in enumerate(self.blocks):
             lw = self._layer(i)
+            mx = mxl[i] if mxl is not None else None
             m = mod[6 * i:6 * i + 6]
             # self attention
             if i == 0 and reuse:
@@ -618,9 +676,9 @@ class WanModel(nn.Module):
                 ops.ln_modulate(x, m[1], m[0], True, eps, ws['h'], round_norm_bf16=(i == 0))
                 custom = _replaced_forward(blk.self_attn)
                 if custom is None:
-                    ops.gemm(ws['h'], lw['wqkv'], lw['bqkv'], ops.BIAS_BF16, ws['qkv'])
+                    self._linear('wqkv', ws['h'], qd, lw, mx, lw['bqkv'], ops.BIAS_BF16, ws['qkv'])
                     self._self_attention(ws, blk, grid, rope, L, pos0)
-                    ops.gemm(ws['a'], lw['self_attn.o'], blk.self_attn.o.bias, ops.GATE_RESID_F32, x, gate=m[2])
+                    self._linear('self_attn.o', ws['a'], qd, lw, mx, blk.self_attn.o.bias, ops.GATE_RESID_F32, x, gate=m[2])
                 else:
                     # operator seam (2) of the reference (text2video.py:97-100): the caller replaced
                     # block.self_attn.forward — call it with the reference's arguments and keep the fused rest
@@ -636,7 +694,7 @@ class WanModel(nn.Module):
                     self._cross_kv(i, lw, ctx_emb, row_major=True) + ('row-major',)
             kc, vc = ctx_layers[i][:2]
             ops.ln_modulate(x, blk.norm3.weight, blk.norm3.bias, False, eps, ws['h'])
-            ops.gemm(ws['h'], lw['cross_attn.q'], ca.q.bias, ops.BIAS_BF16, ws['q'])
+            self._linear('cross_attn.q', ws['h'], qd, lw, mx, ca.q.bias, ops.BIAS_BF16, ws['q'])
             ops.rmsnorm_rope(ws['q'], ca.norm_q.weight, eps, d // self.num_heads, ws['k'],
                              out_scale=self._q_scale() if fa is None else 1.0)
             if fa is not None:
@@ -649,11 +707,11 @@ class WanModel(nn.Module):
                 self._cross_attention_head_sharded(ws, kc, vc)
             else:
                 self._attention(ws['k'], kc, vc, ws['a'], self.text_len, self.num_heads)
-            ops.gemm(ws['a'], lw['cross_attn.o'], ca.o.bias, ops.GATE_RESID_F32, x, gate=None)
+            self._linear('cross_attn.o', ws['a'], qd, lw, mx, ca.o.bias, ops.GATE_RESID_F32, x, gate=None)
             # ffn
             ops.ln_modulate(x, m[4], m[3], True, eps, ws['h'])
-            ops.gemm(ws['h'], lw['ffn.0'], blk.ffn['0'].bias, ops.BIAS_GELU_BF16, ws['u'])
-            ops.gemm(ws['u'], lw['ffn.2'], blk.ffn['2'].bias, ops.GATE_RESID_F32, x, gate=m[5])
+            self._linear('ffn.0', ws['h'], qd, lw, mx, blk.ffn['0'].bias, ops.BIAS_GELU_BF16, ws['u'])
+            self._linear('ffn.2', ws['u'], qf, lw, mx, blk.ffn['2'].bias, ops.GATE_RESID_F32, x, gate=m[5])
 
         # head (model.py:333-343): fp32 end to end
         ops.ln_modulate(x, ws['hmod'][1], ws['hmod'][0], True, eps, ws['hf'])

@@ -30,7 +30,8 @@ from .utils.fm_solvers_unipc import FlowUniPCMultistepScheduler
 class WanT2V:
 
     def __init__(self, config, checkpoint_dir, device_id=0, rank=0, t5_fsdp=False, dit_fsdp=False, use_usp=False,
-                 t5_cpu=False, text_encoder=None, model=None, vae=None, cfg_parallel=False, vae_parallel=False, use_ring=False, sp_degrees=None):
+                 t5_cpu=False, text_encoder=None, model=None, vae=None, cfg_parallel=False, vae_parallel=False, use_ring=False, sp_degrees=None,
+                 dit_gemm='bf16'):
         self.device = torch.device(f'cuda:{device_id}')
         self.config = config
         self.rank = rank
@@ -91,6 +92,9 @@ class WanT2V:
         if dit_fsdp:
             from .distributed.fsdp import shard_model
             self.model = shard_model(self.model, device_id=device_id)
+        # 'mxfp8' = the six per-block linears on the block-scaled fp8 MFMA (WanModel.set_gemm_precision): opt-in, raises with dit_fsdp
+        if dit_gemm != 'bf16':      # the default leaves a caller-supplied `model=` object untouched
+            self.model.set_gemm_precision(dit_gemm)
         self.sample_neg_prompt = config.sample_neg_prompt
 
     def _encode(self, prompt):

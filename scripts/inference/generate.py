@@ -67,6 +67,8 @@ FLAGS = [
     ('--vae_parallel', dict(nargs='?', const='spatial', default=False, choices=['spatial', 'pipeline'],
                             help='VAE decode over all ranks instead of rank 0 alone: spatial (default) = every rank decodes a band of image columns, '
                                  'pipeline = the decoder layers cut into one segment per rank.')),
+    ('--dit_gemm', dict(type=str, default='bf16', choices=['bf16', 'mxfp8'],
+                        help="arithmetic of the six per-block DiT linears: bf16 (the reference's) or mxfp8 (opt-in, block-scaled fp8 MFMA; not with --dit_fsdp).")),
     ('--prompt_embeds', dict(type=str, default=None, help="torch file {'prompt','negative'} of umT5 embeddings, replaces the text encoder.")),
 ]
 
@@ -153,7 +155,7 @@ def generate(args):
     logging.info('Creating WanT2V pipeline.')
     pipe = wan.WanT2V(config=cfg, checkpoint_dir=args.ckpt_dir, device_id=local, rank=rank, t5_fsdp=args.t5_fsdp,
                       dit_fsdp=args.dit_fsdp, use_usp=(args.ulysses_size > 1 or args.ring_size > 1), t5_cpu=args.t5_cpu,
-                      cfg_parallel=args.cfg_parallel, vae_parallel=args.vae_parallel,
+                      cfg_parallel=args.cfg_parallel, vae_parallel=args.vae_parallel, dit_gemm=args.dit_gemm,
                       sp_degrees=(args.ulysses_size, args.ring_size) if args.ring_size > 1 else None)
     prompt, n_prompt = args.prompt, ''
     if args.prompt_embeds:
