@@ -126,6 +126,26 @@ int mg_gemm_mxfp8(const uint8_t* Aq, int64_t lda, const uint8_t* As, int64_t lda
                   const uint8_t* Ws, int64_t ldws, const float* bias, int64_t M, int N, int K, int epilogue,
                   void* out, int64_t ldo, const float* gate, void* stream);
 
+/* MXFP8 where the activation is produced (pure additions to ABI 9): the two producers below write the operand of the next
+ * mg_gemm_mxfp8 themselves, so the bf16 activation makes no round trip through memory and mg_quant_mxfp8_rows is not run.  Both
+ * emit, byte for byte, what mg_quant_mxfp8_rows makes of the bf16 tensor the bf16 form of the same call stores.
+ *
+ * mg_ln_modulate_mxfp8: mg_ln_modulate with a bf16 output (same arguments, same arithmetic, same rounding to bf16), the bf16 value
+ * then written as e4m3 bytes q [rows][dim] (row stride ldq) and scale bytes scales [rows][dim/32] (row stride lds).  out / ldo:
+ * the bf16 row as well, or NULL — then it is never written.  dim % 128 == 0, dim <= 8192, ldx % 4 == 0, ldq % 16 == 0,
+ * lds % 4 == 0, x / q 16-byte, scales 4-byte and out 8-byte aligned (ldo % 4 == 0), else MG_ERR_SHAPE. */
+int mg_ln_modulate_mxfp8(const float* x, int64_t ldx, int64_t rows, int dim, const float* scale, const float* shift,
+                         int add_one, float eps, int round_norm_bf16, uint16_t* out, int64_t ldo, uint8_t* q,
+                         int64_t ldq, uint8_t* scales, int64_t lds, void* stream);
+
+/* mg_gemm_mxfp8 with the epilogue MG_EPI_BIAS_GELU_BF16 (same operands, same k order, same bits up to the bf16 value
+ * bf16(gelu_tanh(bf16(acc + bias)))), that value stored as e4m3 bytes oq [M][N] (row stride ldoq) and scale bytes oscales
+ * [M][N/32] (row stride ldos) in place of bf16: ffn.0 feeding ffn.2.  N % 32 == 0, ldoq % 16 == 0, ldos % 4 == 0, oq 16-byte
+ * and oscales 4-byte aligned, the rest as mg_gemm_mxfp8, else MG_ERR_SHAPE.  Bytes of a row past N (N/32) are not touched. */
+int mg_gemm_mxfp8_gelu_q(const uint8_t* Aq, int64_t lda, const uint8_t* As, int64_t ldas, const uint8_t* Wq, int64_t ldw,
+                         const uint8_t* Ws, int64_t ldws, const float* bias, int64_t M, int N, int K, uint8_t* oq,
+                         int64_t ldoq, uint8_t* oscales, int64_t ldos, void* stream);
+
 /* softmax(q k^T * scale) v, non-causal, keys >= Lk masked; bf16 in/out, fp32 accumulate,
  * head_dim 128.  Replaces flash_attn_varlen_func as called from
  * wan/modules/attention.py:96-127 (self-attention model.py:146-151, k_lens=seq_lens;

@@ -4,6 +4,7 @@
 //
 // Reference arithmetic (file:line under the reference tree) is named at each kernel.
 #include "common.h"
+#include "mxfp8_quant.h"
 #include "../../include/moviigen_hip.h"
 
 #define NT 256
@@ -11,11 +12,27 @@
 // ---------------------------------------------------------------------------------------------
 // LayerNorm (no affine, eps) + modulate  — wan/modules/model.py:89-99, :299, :306, :307, :340-342
 // ---------------------------------------------------------------------------------------------
-template <int MAXV>
+// ONE kernel text with two output modes.  MX false = mg_ln_modulate (fp32 or bf16 out; `mx` is an empty struct).  MX true =
+// mg_ln_modulate_mxfp8: rounds to bf16 exactly as the bf16 output does and emits that value as MXFP8 (mxfp8_quant.h;
+// include/moviigen_hip.h) — e4m3 bytes mx.q [rows][dim] + scale bytes mx.s [rows][dim / 32] — and stores the bf16 row only when
+// `out` is given.  A thread owns 4 consecutive elements, so 8 neighbouring lanes own a 32-block (its maximum: three __shfl_xor
+// steps), a thread stores one dword of 4 element bytes and 32 lanes assemble one dword of 4 scale bytes.  dim % 128 == 0 keeps every
+// such group of 32 lanes wholly inside or wholly outside the row, so the shuffles only ever read lanes that take the same branch.
+template <bool MX>
+struct LnMxOut {};
+template <>
+struct LnMxOut<true> {
+    uint8_t* q;
+    int64_t ldq;
+    uint8_t* s;
+    int64_t lds;
+};
+
+template <int MAXV, bool MX = false>
 __global__ __launch_bounds__(NT) void ln_modulate_kernel(
     const float* __restrict__ x, int64_t ldx, int64_t rows, int dim, const float* __restrict__ scale,
     const float* __restrict__ shift, int add_one, float eps, int do_round, void* __restrict__ out,
-    int out_f32, int64_t ldo) {
+    int out_f32, int64_t ldo, LnMxOut<MX> mx) {
     __shared__ float red[NT / 64];
     const int nv = dim >> 2;
     const float inv_dim = 1.f / (float)dim;
@@ -60,7 +77,25 @@ __global__ __launch_bounds__(NT) void ln_modulate_kernel(
                 }
                 const float o0 = y[0] * sc.x + sh.x, o1 = y[1] * sc.y + sh.y, o2 = y[2] * sc.z + sh.z,
                             o3 = y[3] * sc.w + sh.w;
-                if (out_f32) {
+                if constexpr (MX) {
+                    uint2 p;
+                    p.x = pack_bf2(o0, o1);
+                    p.y = pack_bf2(o2, o3);
+                    if (out) ((uint2*)((uint16_t*)out + row * ldo))[c] = p;
+                    const float f0 = __uint_as_float(p.x << 16), f1 = __uint_as_float(p.x & 0xffff0000u),
+                                f2 = __uint_as_float(p.y << 16), f3 = __uint_as_float(p.y & 0xffff0000u);
+                    float amax = fmaxf(fmaxf(fabsf(f0), fabsf(f1)), fmaxf(fabsf(f2), fabsf(f3)));
+                    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+                    amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+                    amax = fmaxf(amax, __shfl_xor(amax, 4, 64));
+                    const int e = mx_block_exp(amax);
+                    ((unsigned*)(mx.q + row * mx.ldq))[c] = mx_pack4(f0, f1, f2, f3, mx_inv_scale(e));
+                    const unsigned sbyte = (unsigned)(e + 127);
+                    const int lane = threadIdx.x & 63, base = lane & ~31;
+                    const unsigned s0 = __shfl(sbyte, base, 64), s1 = __shfl(sbyte, base + 8, 64), s2 = __shfl(sbyte, base + 16, 64),
+                                   s3 = __shfl(sbyte, base + 24, 64);
+                    if ((lane & 31) == 0) *(unsigned*)(mx.s + row * mx.lds + (c >> 3)) = s0 | (s1 << 8) | (s2 << 16) | (s3 << 24);
+                } else if (out_f32) {
                     ((float4*)((float*)out + row * ldo))[c] = make_float4(o0, o1, o2, o3);
                 } else {
                     uint2 p;
@@ -85,13 +120,39 @@ extern "C" int mg_ln_modulate(const float* x, int64_t ldx, int64_t rows, int dim
     const int nv = dim >> 2;
     if (nv <= 2 * NT)
         hipLaunchKernelGGL(ln_modulate_kernel<2>, dim3(grid), dim3(NT), 0, st, x, ldx, rows, dim, scale,
-                           shift, add_one, eps, round_norm_bf16, out, out_f32, ldo);
+                           shift, add_one, eps, round_norm_bf16, out, out_f32, ldo, LnMxOut<false>{});
     else if (nv <= 5 * NT)
         hipLaunchKernelGGL(ln_modulate_kernel<5>, dim3(grid), dim3(NT), 0, st, x, ldx, rows, dim, scale,
-                           shift, add_one, eps, round_norm_bf16, out, out_f32, ldo);
+                           shift, add_one, eps, round_norm_bf16, out, out_f32, ldo, LnMxOut<false>{});
     else
         hipLaunchKernelGGL(ln_modulate_kernel<8>, dim3(grid), dim3(NT), 0, st, x, ldx, rows, dim, scale,
-                           shift, add_one, eps, round_norm_bf16, out, out_f32, ldo);
+                           shift, add_one, eps, round_norm_bf16, out, out_f32, ldo, LnMxOut<false>{});
+    return mg_check_launch();
+}
+
+extern "C" int mg_ln_modulate_mxfp8(const float* x, int64_t ldx, int64_t rows, int dim, const float* scale, const float* shift,
+                                    int add_one, float eps, int round_norm_bf16, uint16_t* out, int64_t ldo, uint8_t* q,
+                                    int64_t ldq, uint8_t* scales, int64_t lds, void* stream) {
+    if (rows == 0) return MG_OK;  // empty input (data pointers of empty tensors are NULL)
+    if (!x || !q || !scales) return MG_ERR_ARG;
+    if (dim <= 0 || (dim % 128) || dim > 8192 || (ldx & 3) || ldx < dim || ldq < dim || lds < dim / 32) return MG_ERR_SHAPE;
+    if ((ldq & 15) || (lds & 3) || ((uintptr_t)x & 15) || ((uintptr_t)q & 15) || ((uintptr_t)scales & 3)) return MG_ERR_SHAPE;
+    if (out && ((ldo & 3) || ldo < dim || ((uintptr_t)out & 7))) return MG_ERR_SHAPE;
+    if ((scale && ((uintptr_t)scale & 15)) || (shift && ((uintptr_t)shift & 15))) return MG_ERR_SHAPE;
+    if (rows <= 0) return MG_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = (int)(rows < 65536 * 4 ? rows : 65536 * 4);
+    const int nv = dim >> 2;
+    const LnMxOut<true> mxo = {q, ldq, scales, lds};
+    if (nv <= 2 * NT)
+        hipLaunchKernelGGL((ln_modulate_kernel<2, true>), dim3(grid), dim3(NT), 0, st, x, ldx, rows, dim, scale, shift, add_one, eps,
+                           round_norm_bf16, (void*)out, 0, ldo, mxo);
+    else if (nv <= 5 * NT)
+        hipLaunchKernelGGL((ln_modulate_kernel<5, true>), dim3(grid), dim3(NT), 0, st, x, ldx, rows, dim, scale, shift, add_one, eps,
+                           round_norm_bf16, (void*)out, 0, ldo, mxo);
+    else
+        hipLaunchKernelGGL((ln_modulate_kernel<8, true>), dim3(grid), dim3(NT), 0, st, x, ldx, rows, dim, scale, shift, add_one, eps,
+                           round_norm_bf16, (void*)out, 0, ldo, mxo);
     return mg_check_launch();
 }
 

@@ -10,6 +10,7 @@
 // (the residual GEMM ran 13 % below the same shape with a plain bf16 store).
 #pragma once
 #include "common.h"
+#include "mxfp8_quant.h"
 #include "../../include/moviigen_hip.h"
 
 template <int EPI, int NI, int NJ>
@@ -226,4 +227,80 @@ MG_DEV void mg_gemm_epilogue16(const f32x4_t (&acc)[NI][NJ], int64_t m_wave, int
         mg_gemm_epilogue16_impl<EPI, NI, NJ, true, false>(acc, m_wave, n_wave, r16, G, M, N, bias, gate, out, ldo);
     else
         mg_gemm_epilogue16_impl<EPI, NI, NJ, false, false>(acc, m_wave, n_wave, r16, G, M, N, bias, gate, out, ldo);
+}
+
+// The GELU epilogue whose result leaves as MXFP8 (mg_gemm_mxfp8_gelu_q): the value is bf16(gelu_tanh(bf16(acc + bias))), exactly
+// what MG_EPI_BIAS_GELU_BF16 stores, written as e4m3 bytes oq[M][N] + scale bytes os[M][N / 32] (mxfp8_quant.h) — the bytes the
+// stand-alone quantiser makes of that bf16 row.  N % 32 == 0 and n_wave % 128 == 0, so a 32-block of a row is whole or absent.
+// Lane (r16, G) holds, of the row's block b of the wave's four, features 32 b + 4 G .. + 3 (feature block 2 b) and 32 b + 16 + 4 G ..
+// + 3 (feature block 2 b + 1): 8 values; the block's maximum is theirs across the four lanes r16 + 16 G (lanes 16 and 32 apart).
+// The shuffles run in every lane (rows >= M carry finite junk, nothing of it is stored); only the stores are guarded.  The four
+// scale bytes of a row are one aligned dword, collected over b in one register per token block and stored by the G == 0 lanes;
+// where the wave's 128 features are not all there (FULL false) lane G stores the byte of block G, if that block exists.
+// Block outer, token block inner, as in mg_gemm_epilogue16_impl: the bias of one block (8 registers) is live at a time.
+template <int NI, int NJ, bool FULL, bool FULLM>
+MG_DEV void mg_gemm_epilogue16_gelu_q_impl(const f32x4_t (&acc)[NI][NJ], int64_t m_wave, int n_wave, int r16, int G,
+                                           int64_t M, int N, const float* __restrict__ bias, uint8_t* __restrict__ oq, int64_t ldoq,
+                                           uint8_t* __restrict__ os, int64_t ldos) {
+    static_assert(NI == 8, "four 32-blocks = one dword of scale bytes per row");
+    unsigned sdw[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) sdw[j] = 0u;
+#pragma unroll
+    for (int b = 0; b < NI / 2; ++b) {
+        const int n = n_wave + b * 32 + G * 4;
+        if (!FULL && n_wave + b * 32 >= N) continue;                  // wave-uniform
+        float4 b0 = make_float4(0.f, 0.f, 0.f, 0.f), b1 = b0;
+        if (bias) {
+            b0 = *(const float4*)(bias + n);
+            b1 = *(const float4*)(bias + n + 16);
+        }
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int64_t m = m_wave + j * 16 + r16;
+            float v[8] = {acc[2 * b][j][0] + b0.x,     acc[2 * b][j][1] + b0.y,     acc[2 * b][j][2] + b0.z,     acc[2 * b][j][3] + b0.w,
+                          acc[2 * b + 1][j][0] + b1.x, acc[2 * b + 1][j][1] + b1.y, acc[2 * b + 1][j][2] + b1.z, acc[2 * b + 1][j][3] + b1.w};
+            float amax = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                v[e] = round_bf(gelu_tanh(round_bf(v[e])));               // the bf16 Linear output, GELU, the bf16 value of ffn.1
+                amax = fmaxf(amax, fabsf(v[e]));
+            }
+            amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
+            amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+            const int ex = mx_block_exp(amax);
+            const float inv = mx_inv_scale(ex);
+            sdw[j] |= (unsigned)(ex + 127) << (8 * b);
+            const unsigned p0 = mx_pack4(v[0], v[1], v[2], v[3], inv), p1 = mx_pack4(v[4], v[5], v[6], v[7], inv);
+            if (FULLM || m < M) {
+                uint8_t* o = oq + m * ldoq + n;
+                *(unsigned*)o = p0;
+                *(unsigned*)(o + 16) = p1;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int64_t m = m_wave + j * 16 + r16;
+        if (!FULLM && m >= M) continue;
+        uint8_t* s = os + m * ldos + (n_wave >> 5);
+        if (FULL) {
+            if (G == 0) *(unsigned*)s = sdw[j];
+        } else if (n_wave + G * 32 < N) {
+            s[G] = (uint8_t)(sdw[j] >> (8 * G));
+        }
+    }
+}
+
+template <int NI, int NJ>
+MG_DEV void mg_gemm_epilogue16_gelu_q(const f32x4_t (&acc)[NI][NJ], int64_t m_wave, int n_wave, int r16, int G, int64_t M,
+                                      int N, const float* __restrict__ bias, uint8_t* __restrict__ oq, int64_t ldoq,
+                                      uint8_t* __restrict__ os, int64_t ldos) {
+    if (n_wave >= N) return;                                           // wave-uniform: none of the wave's features exist
+    if (n_wave + NI * 16 <= N && m_wave + NJ * 16 <= M)
+        mg_gemm_epilogue16_gelu_q_impl<NI, NJ, true, true>(acc, m_wave, n_wave, r16, G, M, N, bias, oq, ldoq, os, ldos);
+    else if (n_wave + NI * 16 <= N)
+        mg_gemm_epilogue16_gelu_q_impl<NI, NJ, true, false>(acc, m_wave, n_wave, r16, G, M, N, bias, oq, ldoq, os, ldos);
+    else
+        mg_gemm_epilogue16_gelu_q_impl<NI, NJ, false, false>(acc, m_wave, n_wave, r16, G, M, N, bias, oq, ldoq, os, ldos);
 }

@@ -1,6 +1,7 @@
 // MXFP8 (OCP e4m3fn elements, one E8M0 scale byte per 32 consecutive k) for the DiT linear layers on gfx950 (CDNA4):
 //   mg_quant_mxfp8_rows   bf16 [rows][K] -> e4m3 bytes [rows][K] + scale bytes [rows][K/32]        (HBM-bound)
 //   mg_gemm_mxfp8         out[M][N] = A[M][K] . W[N][K]^T on v_mfma_scale_f32_16x16x128_f8f6f4, the bf16 GEMM's epilogues
+//   mg_gemm_mxfp8_gelu_q  the same product; the GELU epilogue's bf16 value leaves as MXFP8 (the next GEMM's operand), not as bf16
 // The format (include/moviigen_hip.h has the full paragraph): block of 32 with maximum magnitude amax takes
 // e = clamp(floor(log2 amax) - 8, -127, 127) (a zero block: -127), scale byte e + 127, element = e4m3_rne(clamp(x 2^-e, +-448)).
 //
@@ -23,6 +24,7 @@
 // Accumulation: k-tiles ascending, fp32, one workgroup per output tile, no atomics: the result does not depend on the launch.
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "mxfp8_quant.h"
 #include "../../include/moviigen_hip.h"
 
 #define MX_BM 256
@@ -76,18 +78,7 @@ MG_DEV void mx_wait4(i32x4_t& l0, i32x4_t& h0, int& s0, i32x4_t& l1, i32x4_t& h1
 // ---------------------------------------------------------------------------------------------------------------------
 // quantiser
 // ---------------------------------------------------------------------------------------------------------------------
-// fp32 -> e4m3fn, round to nearest even, |y| <= 448 on entry (the caller clamps first).  Integer arithmetic, so that the
-// bytes are defined by this text and not by a conversion instruction's mode bits: normal range rounds the 23-bit mantissa
-// to 3 bits with the carry running into the exponent; below 2^-6 the sum y + 2^14 leaves round(y * 2^9) in its low bits.
-MG_DEV unsigned mx_e4m3(float y) {
-    const unsigned b = __float_as_uint(y), sign = (b >> 24) & 0x80u;
-    unsigned a = b & 0x7fffffffu;
-    if (a < 0x3c800000u)                                               // < 2^-6: e4m3 subnormal (or zero)
-        return sign | (__float_as_uint(__uint_as_float(a) + 16384.0f) - 0x46800000u);
-    a += 0x7ffffu + ((a >> 20) & 1u);
-    return sign | ((a >> 20) - (120u << 3));
-}
-
+// element and scale arithmetic: mxfp8_quant.h (mx_e4m3, mx_block_exp, mx_inv_scale, mx_pack4)
 // One wave per row; a lane owns 16 consecutive elements (two 16-byte loads, one 16-byte store), a lane PAIR one 32-block,
 // eight lanes the 4 scale bytes of 128 elements = one dword store.  K % 128 == 0 keeps every such group whole.
 __global__ __launch_bounds__(256) void quant_mxfp8_rows_kernel(const uint16_t* __restrict__ x, int64_t ldx, int64_t rows, int K,
@@ -119,11 +110,9 @@ __global__ __launch_bounds__(256) void quant_mxfp8_rows_kernel(const uint16_t* _
 #pragma unroll
         for (int i = 0; i < 16; ++i) amax = fmaxf(amax, fabsf(f[i]));
         amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-        // floor(log2 amax) = the biased exponent - 127 (a bf16 subnormal or zero lands below the clamp either way)
-        int e = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 127 - 8;
-        e = e < -127 ? -127 : e;                                        // the upper clamp (127) cannot be reached from a finite fp32
+        const int e = mx_block_exp(amax);
         const unsigned sbyte = (unsigned)(e + 127);
-        const float inv = __uint_as_float((unsigned)(127 - e) << 23);   // 2^-e, 127 - e in [8, 254]
+        const float inv = mx_inv_scale(e);
         unsigned o[4];
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
@@ -163,12 +152,23 @@ extern "C" int mg_quant_mxfp8_rows(const uint16_t* x, int64_t ldx, int64_t rows,
 // ---------------------------------------------------------------------------------------------------------------------
 // GEMM
 // ---------------------------------------------------------------------------------------------------------------------
+// EPI of the kernel only (mg_gemm_mxfp8_gelu_q): the GELU epilogue whose bf16 value is stored as e4m3 bytes (out, ldo) + scale bytes
+// (qo.s, qo.lds).  The MG_EPI_* instantiations take an empty struct there: ONE kernel text, and their code does not change.
+#define MX_EPI_GELU_Q 100
+template <bool Q>
+struct MxQOut {};
+template <>
+struct MxQOut<true> {
+    uint8_t* s;
+    int64_t lds;
+};
+
 template <int EPI>
 __global__ __launch_bounds__(MX_THREADS, 1) void gemm_mxfp8_kernel(
     const uint8_t* __restrict__ A, int64_t lda, const uint8_t* __restrict__ As, int64_t ldas,
     const uint8_t* __restrict__ Wt, int64_t ldw, const uint8_t* __restrict__ Ws, int64_t ldws,
     const float* __restrict__ bias, int64_t M, int N, int K, void* __restrict__ out, int64_t ldo,
-    const float* __restrict__ gate, int tiles_m, int tiles_n) {
+    const float* __restrict__ gate, int tiles_m, int tiles_n, MxQOut<EPI == MX_EPI_GELU_Q> qo) {
     __shared__ __attribute__((aligned(16))) char smem[2 * MX_STAGE];
 
     const int nwg = gridDim.x, bid = blockIdx.x;
@@ -339,7 +339,10 @@ __global__ __launch_bounds__(MX_THREADS, 1) void gemm_mxfp8_kernel(
             }
         }
         // ---- epilogue (gemm_epilogue.h) of THIS tile; the next tile's first k-tile is already on its way ----
-        mg_gemm_epilogue16<EPI, 8, 8>(acc, m0 + wm * 128, n0 + wn * 128, r16, G, M, N, bias, gate, out, ldo);
+        if constexpr (EPI == MX_EPI_GELU_Q)
+            mg_gemm_epilogue16_gelu_q<8, 8>(acc, m0 + wm * 128, n0 + wn * 128, r16, G, M, N, bias, (uint8_t*)out, ldo, qo.s, qo.lds);
+        else
+            mg_gemm_epilogue16<EPI, 8, 8>(acc, m0 + wm * 128, n0 + wn * 128, r16, G, M, N, bias, gate, out, ldo);
         if (!has_next) break;
         pos = next_pos;
         m0 = m0n;
@@ -347,35 +350,50 @@ __global__ __launch_bounds__(MX_THREADS, 1) void gemm_mxfp8_kernel(
     }
 }
 
-extern "C" int mg_gemm_mxfp8(const uint8_t* Aq, int64_t lda, const uint8_t* As, int64_t ldas, const uint8_t* Wq, int64_t ldw,
-                             const uint8_t* Ws, int64_t ldws, const float* bias, int64_t M, int N, int K, int epilogue,
-                             void* out, int64_t ldo, const float* gate, void* stream) {
-    if (!Aq || !As || !Wq || !Ws || !out) return MG_ERR_ARG;
-    if (epilogue < 0 || epilogue > 3) return MG_ERR_ARG;
+// what both entry points ask of the operands
+static int mx_gemm_check(const uint8_t* Aq, int64_t lda, const uint8_t* As, int64_t ldas, const uint8_t* Wq, int64_t ldw,
+                         const uint8_t* Ws, int64_t ldws, const float* bias, int64_t M, int N, int K) {
+    if (!Aq || !As || !Wq || !Ws) return MG_ERR_ARG;
     if (M < 0 || N <= 0 || K <= 0 || (K % MX_BK) || (N % 16)) return MG_ERR_SHAPE;
-    if (lda < K || ldw < K || ldas < K / 32 || ldws < K / 32 || ldo < N) return MG_ERR_SHAPE;
-    if ((lda & 15) || (ldw & 15) || (ldas & 3) || (ldws & 3) || (ldo & 3)) return MG_ERR_SHAPE;
-    if (((uintptr_t)Aq & 15) || ((uintptr_t)Wq & 15) || ((uintptr_t)As & 3) || ((uintptr_t)Ws & 3) || ((uintptr_t)out & 15))
-        return MG_ERR_SHAPE;
+    if (lda < K || ldw < K || ldas < K / 32 || ldws < K / 32) return MG_ERR_SHAPE;
+    if ((lda & 15) || (ldw & 15) || (ldas & 3) || (ldws & 3)) return MG_ERR_SHAPE;
+    if (((uintptr_t)Aq & 15) || ((uintptr_t)Wq & 15) || ((uintptr_t)As & 3) || ((uintptr_t)Ws & 3)) return MG_ERR_SHAPE;
     if (bias && ((uintptr_t)bias & 15)) return MG_ERR_SHAPE;
-    if (gate && ((uintptr_t)gate & 15)) return MG_ERR_SHAPE;
-    if (M == 0) return MG_OK;
+    return MG_OK;
+}
+// and the launch geometry (M > 0)
+static int mx_gemm_grid(int64_t M, int N, int* tiles_m, int* tiles_n, int* nwg) {
     int n_cu = mg_cu_count();
     if (n_cu < 0) return MG_ERR_LAUNCH;
     n_cu &= ~7;                                         // one workgroup per CU (132 KiB LDS), a multiple of the 8 XCDs
     if (n_cu < 8) n_cu = 8;
     const int64_t tiles_m64 = (M + MX_BM - 1) / MX_BM;
-    const int tiles_n = (N + MX_BN - 1) / MX_BN;
-    if (tiles_m64 * tiles_n > 0x7fffffffLL) return MG_ERR_SHAPE;
-    const int tiles_m = (int)tiles_m64;
-    const int total = tiles_m * tiles_n;
-    int nwg = n_cu;
-    if (total < nwg) nwg = (total + 7) & ~7;          // few tiles: one iteration, still a multiple of 8 (idle ones return)
+    *tiles_n = (N + MX_BN - 1) / MX_BN;
+    if (tiles_m64 * *tiles_n > 0x7fffffffLL) return MG_ERR_SHAPE;
+    *tiles_m = (int)tiles_m64;
+    const int total = *tiles_m * *tiles_n;
+    *nwg = n_cu;
+    if (total < *nwg) *nwg = (total + 7) & ~7;          // few tiles: one iteration, still a multiple of 8 (idle ones return)
+    return MG_OK;
+}
+
+extern "C" int mg_gemm_mxfp8(const uint8_t* Aq, int64_t lda, const uint8_t* As, int64_t ldas, const uint8_t* Wq, int64_t ldw,
+                             const uint8_t* Ws, int64_t ldws, const float* bias, int64_t M, int N, int K, int epilogue,
+                             void* out, int64_t ldo, const float* gate, void* stream) {
+    if (!out) return MG_ERR_ARG;
+    int rc = mx_gemm_check(Aq, lda, As, ldas, Wq, ldw, Ws, ldws, bias, M, N, K);
+    if (rc == MG_ERR_ARG || epilogue < 0 || epilogue > 3) return MG_ERR_ARG;
+    if (rc != MG_OK) return rc;
+    if (ldo < N || (ldo & 3) || ((uintptr_t)out & 15)) return MG_ERR_SHAPE;
+    if (gate && ((uintptr_t)gate & 15)) return MG_ERR_SHAPE;
+    if (M == 0) return MG_OK;
+    int tiles_m, tiles_n, nwg;
+    if ((rc = mx_gemm_grid(M, N, &tiles_m, &tiles_n, &nwg)) != MG_OK) return rc;
     const dim3 grid((unsigned)nwg), block(MX_THREADS);
     hipStream_t st = (hipStream_t)stream;
 #define LAUNCH(E)                                                                                                    \
     hipLaunchKernelGGL((gemm_mxfp8_kernel<E>), grid, block, 0, st, Aq, lda, As, ldas, Wq, ldw, Ws, ldws, bias, M, N, K, \
-                       out, ldo, gate, tiles_m, tiles_n)
+                       out, ldo, gate, tiles_m, tiles_n, MxQOut<false>{})
     switch (epilogue) {
         case MG_EPI_BIAS_BF16: LAUNCH(MG_EPI_BIAS_BF16); break;
         case MG_EPI_BIAS_GELU_BF16: LAUNCH(MG_EPI_BIAS_GELU_BF16); break;
@@ -383,5 +401,22 @@ extern "C" int mg_gemm_mxfp8(const uint8_t* Aq, int64_t lda, const uint8_t* As, 
         default: LAUNCH(MG_EPI_BIAS_F32); break;
     }
 #undef LAUNCH
+    return mg_check_launch();
+}
+
+extern "C" int mg_gemm_mxfp8_gelu_q(const uint8_t* Aq, int64_t lda, const uint8_t* As, int64_t ldas, const uint8_t* Wq,
+                                    int64_t ldw, const uint8_t* Ws, int64_t ldws, const float* bias, int64_t M, int N, int K,
+                                    uint8_t* oq, int64_t ldoq, uint8_t* oscales, int64_t ldos, void* stream) {
+    if (!oq || !oscales) return MG_ERR_ARG;
+    int rc = mx_gemm_check(Aq, lda, As, ldas, Wq, ldw, Ws, ldws, bias, M, N, K);
+    if (rc != MG_OK) return rc;
+    if ((N % 32) || ldoq < N || ldos < N / 32 || (ldoq & 15) || (ldos & 3)) return MG_ERR_SHAPE;
+    if (((uintptr_t)oq & 15) || ((uintptr_t)oscales & 3)) return MG_ERR_SHAPE;
+    if (M == 0) return MG_OK;
+    int tiles_m, tiles_n, nwg;
+    if ((rc = mx_gemm_grid(M, N, &tiles_m, &tiles_n, &nwg)) != MG_OK) return rc;
+    const MxQOut<true> qo = {oscales, ldos};
+    hipLaunchKernelGGL((gemm_mxfp8_kernel<MX_EPI_GELU_Q>), dim3((unsigned)nwg), dim3(MX_THREADS), 0, (hipStream_t)stream, Aq, lda,
+                       As, ldas, Wq, ldw, Ws, ldws, bias, M, N, K, (void*)oq, ldoq, (const float*)nullptr, tiles_m, tiles_n, qo);
     return mg_check_launch();
 }

@@ -29,6 +29,9 @@ SIGNATURES = {
     'mg_quant_mxfp8_rows': [c_vp, c_i64, c_i64, c_int, c_vp, c_i64, c_vp, c_i64, c_vp],
     'mg_gemm_mxfp8': [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_int, c_vp, c_i64,
                       c_vp, c_vp],
+    'mg_ln_modulate_mxfp8': [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_int, c_f32, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp],
+    'mg_gemm_mxfp8_gelu_q': [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_i64,
+                             c_vp],
     'mg_attn_workspace_bytes': [],
     'mg_attn_fwd_bf16_hd128': [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_f32, c_vp, c_vp],
     'mg_attn_fwd_bf16_hd128_lse': [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_f32, c_vp, c_vp],

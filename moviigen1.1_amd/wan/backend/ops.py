@@ -120,6 +120,36 @@ def gemm_mxfp8(aq, a_scales, wq, w_scales, bias, epilogue, out, gate=None):
     return out
 
 
+def ln_modulate_mxfp8(x, scale, shift, add_one, eps, q, scales, out=None, round_norm_bf16=False):
+    """ln_modulate (bf16 result) leaving as MXFP8: x [rows, dim] fp32 -> q uint8 [rows, dim] + scales uint8 [rows, dim/32], the bytes
+    quant_mxfp8 makes of ln_modulate's bf16 output; `out` (bf16 [rows, dim]) receives that output as well when given."""
+    _chk(x, torch.float32, 'x'); _chk(scale, torch.float32, 'scale'); _chk(shift, torch.float32, 'shift')
+    _chk(q, torch.uint8, 'q'); _chk(scales, torch.uint8, 'scales'); _chk(out, torch.bfloat16, 'out')
+    rows, dim = x.shape
+    if tuple(q.shape) != (rows, dim) or tuple(scales.shape) != (rows, dim // 32) or (out is not None and tuple(out.shape) != (rows, dim)):
+        raise lib.MoviigenHipError(f'ln_modulate_mxfp8 shape mismatch x{tuple(x.shape)} q{tuple(q.shape)} scales{tuple(scales.shape)}')
+    lib.call('mg_ln_modulate_mxfp8', _p(x), x.stride(0), rows, dim, _p(scale), _p(shift), int(add_one), float(eps),
+             int(round_norm_bf16), _p(out), 0 if out is None else out.stride(0), _p(q), q.stride(0), _p(scales), scales.stride(0), _st())
+    return q, scales
+
+
+def gemm_mxfp8_gelu_q(aq, a_scales, wq, w_scales, bias, oq, o_scales):
+    """gemm_mxfp8 with the BIAS_GELU_BF16 epilogue whose bf16 result leaves as MXFP8: oq uint8 [M, N] + o_scales uint8 [M, N/32], the
+    bytes quant_mxfp8 makes of that epilogue's output."""
+    _chk(aq, torch.uint8, 'aq'); _chk(a_scales, torch.uint8, 'a_scales'); _chk(wq, torch.uint8, 'wq')
+    _chk(w_scales, torch.uint8, 'w_scales'); _chk(bias, torch.float32, 'bias'); _chk(oq, torch.uint8, 'oq')
+    _chk(o_scales, torch.uint8, 'o_scales')
+    M, K = aq.shape
+    N = wq.shape[0]
+    if (wq.shape[1] != K or tuple(oq.shape) != (M, N) or tuple(o_scales.shape) != (M, N // 32)
+            or tuple(a_scales.shape) != (M, K // 32) or tuple(w_scales.shape) != (N, K // 32)):
+        raise lib.MoviigenHipError(f'gemm_mxfp8_gelu_q shape mismatch aq{tuple(aq.shape)} a_scales{tuple(a_scales.shape)} '
+                                   f'wq{tuple(wq.shape)} w_scales{tuple(w_scales.shape)} oq{tuple(oq.shape)} o_scales{tuple(o_scales.shape)}')
+    lib.call('mg_gemm_mxfp8_gelu_q', _p(aq), aq.stride(0), _p(a_scales), a_scales.stride(0), _p(wq), wq.stride(0), _p(w_scales),
+             w_scales.stride(0), _p(bias), M, N, K, _p(oq), oq.stride(0), _p(o_scales), o_scales.stride(0), _st())
+    return oq, o_scales
+
+
 _ATTN_WS = {}
 
 

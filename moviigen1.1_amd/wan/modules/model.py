@@ -201,6 +201,14 @@ def rope_cos_sin(head_dim, grid, theta=10000.0):
 #   ffn.0           13824   5120  GELU         12.68     12.29   fp8
 #   ffn.2            5120  13824  gate-resid   12.47     12.21   fp8
 MXFP8_SITES = {'wqkv': True, 'self_attn.o': False, 'cross_attn.q': False, 'cross_attn.o': False, 'ffn.0': True, 'ffn.2': True}
+# 'mxfp8' mode: the producers that write an fp8 site's operand themselves (no bf16 round trip, no mg_quant_mxfp8_rows pass).  A producer
+# is True only if it is not slower than its unfused pair in every round of profiles/pr_mxfp8_fused_producers.log:
+#   'ln_modulate'  mg_ln_modulate_mxfp8 in front of wqkv, cross_attn.q and ffn.0 (where that site is fp8 and nothing else reads h)
+#   'gelu'         mg_gemm_mxfp8_gelu_q as ffn.0 when ffn.0 and ffn.2 are both fp8
+# self_attn.o and cross_attn.o take an attention output: they keep the stand-alone quantiser (or stay bf16, as MXFP8_SITES says).
+# That log has not been taken yet (tools/bench_gemm_mxfp8.py 131040 10 10 fused prints the two values): both producers are built and
+# tested (tests/test_mxfp8_fused.py wires them in itself) but stay unwired until it has.
+MXFP8_FUSED_PRODUCERS = {'ln_modulate': False, 'gelu': False}
 GEMM_PRECISIONS = ('bf16', 'mxfp8')
 
 
@@ -248,6 +256,7 @@ class WanModel(nn.Module):
         self._packed = None
         self.gemm_precision = 'bf16'    # set_gemm_precision: 'mxfp8' = the six per-block linears on the block-scaled MFMA (opt-in)
         self._mx = None                 # their quantised weights, built once per set of weights
+        self._mx_fuse = True            # False: every fp8 site quantises its bf16 activation with mg_quant_mxfp8_rows (tests, tools/bench_gemm_mxfp8.py)
         self._ws = {}
         self._rope = {}
         self._ctx_cache = {}
@@ -396,14 +405,25 @@ class WanModel(nn.Module):
                         for lw in self._pack()['layers']]
         return self._mx
 
-    def _linear(self, site, a, act, lw, mx, bias, epilogue, out, gate=None):
+    def _linear(self, site, a, act, lw, mx, bias, epilogue, out, gate=None, quantised=False):
         """one of the six per-block linears: mg_gemm_bf16, or (mxfp8 mode, site enabled) quantise the activation into the
-        workspace and run mg_gemm_mxfp8.  `act` names the activation's quantised buffers in the workspace."""
+        workspace and run mg_gemm_mxfp8.  `act` names the activation's quantised buffers in the workspace; quantised: its producer
+        has filled them already (`a` is then not read)."""
         if mx is None or site not in mx:
             return ops.gemm(a, lw[site], bias, epilogue, out, gate=gate)
         aq, a_s = act
-        ops.quant_mxfp8(a, aq, a_s)
+        if not quantised:
+            ops.quant_mxfp8(a, aq, a_s)
         return ops.gemm_mxfp8(aq, a_s, mx[site][0], mx[site][1], bias, epilogue, out, gate=gate)
+
+    def _ln(self, site, mx, act, x, scale, shift, add_one, h, round_norm_bf16=False):
+        """the LayerNorm + modulate in front of `site`, whose only consumer that site is: straight into the quantised buffers `act` when
+        the site runs on fp8 and the fused producer is wired in (True: h is NOT written), else bf16 into h (False)."""
+        if mx is not None and site in mx and self._mx_fuse and MXFP8_FUSED_PRODUCERS['ln_modulate']:
+            ops.ln_modulate_mxfp8(x, scale, shift, add_one, self.eps, act[0], act[1], round_norm_bf16=round_norm_bf16)
+            return True
+        ops.ln_modulate(x, scale, shift, add_one, self.eps, h, round_norm_bf16=round_norm_bf16)
+        return False
 
     def _layer(self, i):
         """GEMM operands of block i: resident, or (block-sharded mode, wan.distributed.fsdp) views of
@@ -673,15 +693,16 @@ class WanModel(nn.Module):
             if i == 0 and reuse:
                 x.copy_(ws['x0'])                        # block 0 up to here saw the latent and t only: the 'save' forward's stream, bit for bit
             else:
-                ops.ln_modulate(x, m[1], m[0], True, eps, ws['h'], round_norm_bf16=(i == 0))
                 custom = _replaced_forward(blk.self_attn)
                 if custom is None:
-                    self._linear('wqkv', ws['h'], qd, lw, mx, lw['bqkv'], ops.BIAS_BF16, ws['qkv'])
+                    hq = self._ln('wqkv', mx, qd, x, m[1], m[0], True, ws['h'], round_norm_bf16=(i == 0))
+                    self._linear('wqkv', ws['h'], qd, lw, mx, lw['bqkv'], ops.BIAS_BF16, ws['qkv'], quantised=hq)
                     self._self_attention(ws, blk, grid, rope, L, pos0)
                     self._linear('self_attn.o', ws['a'], qd, lw, mx, blk.self_attn.o.bias, ops.GATE_RESID_F32, x, gate=m[2])
                 else:
                     # operator seam (2) of the reference (text2video.py:97-100): the caller replaced
-                    # block.self_attn.forward — call it with the reference's arguments and keep the fused rest
+                    # block.self_attn.forward — call it with the reference's arguments (the bf16 h) and keep the fused rest
+                    ops.ln_modulate(x, m[1], m[0], True, eps, ws['h'], round_norm_bf16=(i == 0))
                     y = custom(ws['h'][None], torch.tensor([Lfull]), torch.tensor([list(grid)]), self.freqs)
                     ops.gate_residual(x, y[0].to(torch.bfloat16).contiguous(), m[2])
                 if i == 0 and share == 'save':
@@ -693,8 +714,8 @@ class WanModel(nn.Module):
                 ctx_layers[i] = self._cross_kv(i, lw, ctx_emb) if fa is None else \
                     self._cross_kv(i, lw, ctx_emb, row_major=True) + ('row-major',)
             kc, vc = ctx_layers[i][:2]
-            ops.ln_modulate(x, blk.norm3.weight, blk.norm3.bias, False, eps, ws['h'])
-            self._linear('cross_attn.q', ws['h'], qd, lw, mx, ca.q.bias, ops.BIAS_BF16, ws['q'])
+            hq = self._ln('cross_attn.q', mx, qd, x, blk.norm3.weight, blk.norm3.bias, False, ws['h'])
+            self._linear('cross_attn.q', ws['h'], qd, lw, mx, ca.q.bias, ops.BIAS_BF16, ws['q'], quantised=hq)
             ops.rmsnorm_rope(ws['q'], ca.norm_q.weight, eps, d // self.num_heads, ws['k'],
                              out_scale=self._q_scale() if fa is None else 1.0)
             if fa is not None:
@@ -709,9 +730,15 @@ class WanModel(nn.Module):
                 self._attention(ws['k'], kc, vc, ws['a'], self.text_len, self.num_heads)
             self._linear('cross_attn.o', ws['a'], qd, lw, mx, ca.o.bias, ops.GATE_RESID_F32, x, gate=None)
             # ffn
-            ops.ln_modulate(x, m[4], m[3], True, eps, ws['h'])
-            self._linear('ffn.0', ws['h'], qd, lw, mx, blk.ffn['0'].bias, ops.BIAS_GELU_BF16, ws['u'])
-            self._linear('ffn.2', ws['u'], qf, lw, mx, blk.ffn['2'].bias, ops.GATE_RESID_F32, x, gate=m[5])
+            hq = self._ln('ffn.0', mx, qd, x, m[4], m[3], True, ws['h'])
+            uq = mx is not None and 'ffn.0' in mx and 'ffn.2' in mx and self._mx_fuse and MXFP8_FUSED_PRODUCERS['gelu']
+            if uq:       # ffn.0's GELU epilogue writes ffn.2's operand: ws['u'] is not written
+                if not hq:
+                    ops.quant_mxfp8(ws['h'], *qd)
+                ops.gemm_mxfp8_gelu_q(qd[0], qd[1], mx['ffn.0'][0], mx['ffn.0'][1], blk.ffn['0'].bias, qf[0], qf[1])
+            else:
+                self._linear('ffn.0', ws['h'], qd, lw, mx, blk.ffn['0'].bias, ops.BIAS_GELU_BF16, ws['u'], quantised=hq)
+            self._linear('ffn.2', ws['u'], qf, lw, mx, blk.ffn['2'].bias, ops.GATE_RESID_F32, x, gate=m[5], quantised=uq)
 
         # head (model.py:333-343): fp32 end to end
         ops.ln_modulate(x, ws['hmod'][1], ws['hmod'][0], True, eps, ws['hf'])
