@@ -423,6 +423,20 @@ int mg_video_to_u8(const float* video, int T, int H, int W, float lo, float hi, 
  * clamp(0,255), truncating cast. */
 int mg_image_to_u8(const float* image, int H, int W, float lo, float hi, uint8_t* pixels, void* stream);
 
+/* The way in (addition to ABI 9; not in the reference, which has no video-to-video start): uint8 RGB frames [T][H0][W0][3] of any size ->
+ * the clip [3][T][H][W] fp32 in [-1,1] that mg_vae_video_in_f32 / WanVAE.encode read.  Resize to cover, centre crop, normalise:
+ *   s = max(H/H0, W/W0) (fp64);  Hs = max(H, floor(H0 s + 0.5)), Ws = max(W, floor(W0 s + 0.5));  crop origin ((Hs-H)/2, (Ws-W)/2), integer division.
+ *   Per axis (in = H0 or W0 samples -> out = Hs or Ws) the antialiased triangle filter with half-pixel centres — what
+ *   F.interpolate(mode='bilinear', antialias=True, align_corners=False) computes: scale = in/out, support = max(scale, 1), for output
+ *   sample i: c = scale (i + 0.5), taps j in [max(0, int(c - support + 0.5)), min(in, int(c + support + 0.5))) with weight
+ *   max(0, 1 - |(j - c + 0.5) / support|), normalised to sum 1.
+ *   r = sum over rows (outer) and columns (inner) of (w_row w_col) v in fp32 on the byte values v in [0, 255], one fixed order (one
+ *   thread per output pixel, no atomics: run-to-run identical);  video = r / 127.5f - 1.0f (an IEEE fp32 division, then a subtraction).
+ * With (H0, W0) == (H, W) every output has the weights {1, 0} per axis and r == v exactly: the result is bitwise (float)v / 127.5f - 1.0f.
+ * MG_ERR_SHAPE: a non-positive size, or Hs > 8 H0, Ws > 8 W0, H0 > 8 Hs or W0 > 8 Ws (more than 8x in either direction; 8x down is
+ * 17 taps per axis), or H or T above 65535.  frames needs no alignment; video is written once, every element. */
+int mg_video_from_u8(const uint8_t* frames, int T, int H0, int W0, int H, int W, float* video, void* stream);
+
 /* time_conv channel halves -> interleaved frames (vae.py:133-137):
  * x [T][H][W][2C] -> out [2T][H][W][C], frame 2t from channels [0,C), 2t+1 from [C,2C). */
 int mg_vae_time_interleave_f32(const float* x, int T, int64_t HW, int C, float* out, void* stream);

@@ -964,6 +964,69 @@ extern "C" int mg_image_to_u8(const float* image, int H, int W, float lo, float 
     return mg_check_launch();
 }
 
+// ---- frame ingest: uint8 frames of any size -> the fp32 clip the encoder reads (mg_video_from_u8, definition in the header) ----
+// One axis of the antialiased triangle filter for one output sample: the taps are the input samples [lo, lo + n), tap k has the
+// raw weight max(0, 1 - |(d0 + k) inv|) with d0 = lo + 0.5 - c, and rnorm = 1 / (sum of the raw weights).  The centre c and the
+// tap range are evaluated in fp64 (c reaches the input extent, where an fp32 ulp is 1e-4 of a pixel: the weights would carry it),
+// the weights themselves in fp32: |d0 + k| <= support + 1 <= 9.
+struct U8Taps { int lo, n; float d0, inv, rnorm; };
+MG_DEV float u8_tap_weight(const U8Taps& a, int k) { return fmaxf(0.f, 1.f - fabsf((a.d0 + (float)k) * a.inv)); }
+MG_DEV U8Taps u8_axis_taps(int i, int in, double scale) {
+    const double support = scale > 1.0 ? scale : 1.0;
+    const double c = scale * (i + 0.5);
+    U8Taps a;
+    a.lo = max(0, (int)(c - support + 0.5));
+    a.n = min(in, (int)(c + support + 0.5)) - a.lo;       // >= 1: the tap under the centre is always inside, with weight >= 0.5
+    a.d0 = (float)(a.lo + 0.5 - c);
+    a.inv = (float)(1.0 / support);
+    float s = 0.f;
+    for (int k = 0; k < a.n; ++k) s += u8_tap_weight(a, k);
+    a.rnorm = 1.f / s;
+    return a;
+}
+
+// one thread per output pixel, all three channels: the taps of neighbouring pixels overlap, so the 3-byte reads of a wave are served
+// by the same cache lines; each of the three stores of a wave is one contiguous run of its channel plane.  The grid is (column
+// blocks, rows, frames): no division to find (t, y, x), and the row taps are the same for a whole workgroup.  (oy, ox): the crop
+// origin in the resized image, sy / sx = input / resized extent.
+__global__ __launch_bounds__(256) void video_from_u8_kernel(const uint8_t* __restrict__ frames, int T, int H0, int W0, int H, int W, int oy, int ox,
+                                                            double sy, double sx, float* __restrict__ out) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, t = blockIdx.z;
+    if (x >= W) return;
+    const int64_t total = (int64_t)T * H * W;
+    const int64_t i = ((int64_t)t * H + y) * W + x;
+    const U8Taps ay = u8_axis_taps(y + oy, H0, sy), ax = u8_axis_taps(x + ox, W0, sx);
+    const uint8_t* const fr = frames + (int64_t)t * H0 * W0 * 3;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    for (int j = 0; j < ay.n; ++j) {                                   // rows outer, columns inner: one fixed order
+        const float wy = u8_tap_weight(ay, j) * ay.rnorm;
+        const uint8_t* row = fr + ((int64_t)(ay.lo + j) * W0 + ax.lo) * 3;
+        for (int k = 0; k < ax.n; ++k) {
+            const float w = wy * (u8_tap_weight(ax, k) * ax.rnorm);
+            a0 += w * (float)row[3 * k];
+            a1 += w * (float)row[3 * k + 1];
+            a2 += w * (float)row[3 * k + 2];
+        }
+    }
+    out[i] = a0 / 127.5f - 1.f;
+    out[total + i] = a1 / 127.5f - 1.f;
+    out[2 * total + i] = a2 / 127.5f - 1.f;
+}
+
+extern "C" int mg_video_from_u8(const uint8_t* frames, int T, int H0, int W0, int H, int W, float* video, void* stream) {
+    if (T <= 0 || H0 <= 0 || W0 <= 0 || H <= 0 || W <= 0) return MG_ERR_SHAPE;      // (first: an empty tensor has no address)
+    if (!frames || !video) return MG_ERR_ARG;
+    const double sh = (double)H / H0, sw = (double)W / W0, s = sh > sw ? sh : sw;
+    const double hs_d = floor(H0 * s + 0.5), ws_d = floor(W0 * s + 0.5);
+    if (hs_d > 8.0 * H0 || ws_d > 8.0 * W0 || hs_d > 0x7fffffff || ws_d > 0x7fffffff) return MG_ERR_SHAPE;      // more than 8x up
+    const int Hs = hs_d > H ? (int)hs_d : H, Ws = ws_d > W ? (int)ws_d : W;
+    if (H0 > 8 * (int64_t)Hs || W0 > 8 * (int64_t)Ws) return MG_ERR_SHAPE;              // more than 8x down: above 17 taps per axis
+    if (H > 65535 || T > 65535) return MG_ERR_SHAPE;                                     // grid dimensions y, z
+    hipLaunchKernelGGL(video_from_u8_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)H, (unsigned)T), dim3(256), 0, (hipStream_t)stream, frames, T, H0, W0, H, W, (Hs - H) / 2, (Ws - W) / 2,
+                       (double)H0 / Hs, (double)W0 / Ws, video);
+    return mg_check_launch();
+}
+
 __global__ void time_interleave_kernel(const float* __restrict__ x, int T, int64_t hw, int C, float* __restrict__ out) {
     // x [T][hw][2C] -> out [2T][hw][C]: frame 2t <- channels [0,C), frame 2t+1 <- [C,2C)  (vae.py:133-137)
     const int64_t total = (int64_t)2 * T * hw * C;

@@ -476,6 +476,21 @@ def video_to_u8(video, lo=-1.0, hi=1.0):
     return out
 
 
+def video_from_u8(frames, H, W, out=None):
+    """uint8 RGB frames [T,H0,W0,3] of any size -> the clip [3,T,H,W] fp32 in [-1,1]: resize to cover (antialiased triangle filter),
+    centre crop, v / 127.5 - 1 (mg_video_from_u8; the definition is in include/moviigen_hip.h)."""
+    _chk(frames, torch.uint8, 'frames'); _chk(out, torch.float32, 'out')
+    if frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise lib.MoviigenHipError(f'frames must be a contiguous uint8 [T, H0, W0, 3] tensor, got {tuple(frames.shape)}')
+    T, H0, W0, _ = frames.shape
+    if out is None:
+        out = torch.empty(3, T, int(H), int(W), dtype=torch.float32, device=frames.device)
+    elif tuple(out.shape) != (3, T, int(H), int(W)) or not out.is_contiguous():
+        raise lib.MoviigenHipError(f'video_from_u8: out must be a contiguous {(3, T, int(H), int(W))} tensor, got {tuple(out.shape)}')
+    lib.call('mg_video_from_u8', _p(frames), T, H0, W0, int(H), int(W), _p(out), _st())
+    return out
+
+
 def gate_residual(x, y, gate=None):
     """x [rows, dim] fp32 += y [rows, dim] bf16 * gate [dim] fp32 (None = 1)."""
     _chk(x, torch.float32, 'x'); _chk(y, torch.bfloat16, 'y'); _chk(gate, torch.float32, 'gate')

@@ -264,7 +264,7 @@ class WanVAE_:
         name = pre + 'resample.1'
         w = self.P[name + '.weight']
         shp = ops.vae_conv_strided_out_shape(x.shape, (1, 3, 3), (1, 2, 2), 0, (0, 1), (0, 1))
-        y = ops.vae_conv_strided(x, w, self.P[name + '.bias'], self._new(*shp, w.shape[0]), (1, 2, 2), 0, (0, 1), (0, 1), mode=self._conv_mode & 0xff)
+        y = ops.vae_conv_strided(x, w, self.P[name + '.bias'], self._new(*shp, w.shape[0]), (1, 2, 2), 0, (0, 1), (0, 1), mode=ops.VAE_EXACT)
         if (pre + 'time_conv.weight') in self.P:
             i = idx[0]
             keep = y[-1:].clone()
@@ -272,7 +272,7 @@ class WanVAE_:
                 wt = self.P[pre + 'time_conv.weight']
                 shp = ops.vae_conv_strided_out_shape(y.shape, (3, 1, 1), (2, 1, 1), 1, (0, 0), (0, 0))
                 y = ops.vae_conv_strided(y, wt, self.P[pre + 'time_conv.bias'], self._new(*shp, wt.shape[0]), (2, 1, 1), 1, cache=cache[i],
-                                         mode=self._conv_mode & 0xff)
+                                         mode=ops.VAE_EXACT)
             cache[i] = keep
             idx[0] += 1
         return y
@@ -289,7 +289,7 @@ class WanVAE_:
         else:
             cx = xs[-1:].clone()
         w = self.P['encoder.conv1.weight']
-        x = ops.vae_conv_in3(xs, w, self.P['encoder.conv1.bias'], self._new(n, H, W, w.shape[0]), cache=prev, mode=self._conv_mode & 0xff)
+        x = ops.vae_conv_in3(xs, w, self.P['encoder.conv1.bias'], self._new(n, H, W, w.shape[0]), cache=prev, mode=ops.VAE_EXACT)
         cache[0] = cx
         del xs, prev
         idx = [1]
@@ -305,11 +305,12 @@ class WanVAE_:
     def encode(self, x):
         """x [3,T,H,W] (fp32 or castable; T >= 1, H, W >= 8) -> the normalised mu [z_dim, 1 + (T-1)//4, H//8, W//8] fp32 on the model's device.
         Chunk 0 is frame 0 alone, chunk i >= 1 the frames 1 + 4(i-1) .. 4i with the encoder's causal caches carried over (the chunking is fixed
-        by the temporal stride: there is nothing to choose); frames behind the last full group of four are not read, as in the reference."""
+        by the temporal stride: there is nothing to choose); frames behind the last full group of four are not read, as in the reference.
+        mode='bf16x3': the stride-1 convolutions (the residual blocks, the head: 94 % of the multiply-adds at 1920x832x81, tools/vae_flops.py) run split-bf16 as in the decoder;
+        the two gathers only the encoder has (the stride-2 down-samplers, the 3-channel input convolution) and the attention block's GEMMs
+        (2.5 % and 3.1 %) stay exact — they have no bf16x3 form."""
         if self.enc_missing:
             raise ValueError('encode needs the encoder half of the checkpoint; the state dict has no ' + ', '.join(self.enc_missing))
-        if self.mode != 'exact':
-            raise ValueError("encode runs in the reference's fp32 arithmetic only (mode='exact'): the strided and the input convolution have no bf16x3 form")
         if not torch.is_tensor(x) or x.dim() != 4 or x.shape[0] != 3 or x.shape[1] < 1 or x.shape[2] < 8 or x.shape[3] < 8:
             raise ValueError(f'encode expects a video tensor [3, T >= 1, H >= 8, W >= 8], got {tuple(x.shape) if torch.is_tensor(x) else type(x)}')
         x = x.to(self.device, torch.float32).contiguous()

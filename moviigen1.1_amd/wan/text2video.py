@@ -27,6 +27,15 @@ from .utils.fm_solvers import FlowDPMSolverMultistepScheduler, get_sampling_sigm
 from .utils.fm_solvers_unipc import FlowUniPCMultistepScheduler
 
 
+def v2v_steps(sampling_steps, strength):
+    """(n_run, i0) of a video-to-video start: the last n_run = min(max(int(sampling_steps * strength), 1), sampling_steps) steps of the
+    schedule run, beginning at index i0 = sampling_steps - n_run (the img2img convention); 0 < strength <= 1."""
+    if not 0.0 < float(strength) <= 1.0:
+        raise ValueError(f'strength must be in (0, 1], got {strength!r}')
+    n_run = min(max(int(sampling_steps * float(strength)), 1), sampling_steps)
+    return n_run, sampling_steps - n_run
+
+
 class WanT2V:
 
     def __init__(self, config, checkpoint_dir, device_id=0, rank=0, t5_fsdp=False, dit_fsdp=False, use_usp=False,
@@ -109,9 +118,47 @@ class WanT2V:
                 'WanT2V(text_encoder=callable)')
         return [t.to(self.device) for t in self.text_encoder([prompt], self.device)]
 
+    def init_clip(self, init_video, size, frame_num):
+        """`generate`'s init_video -> the clip [3, frame_num, size[1], size[0]] fp32 in [-1, 1] on the device."""
+        if not torch.is_tensor(init_video):
+            init_video = torch.as_tensor(init_video)
+        W_, H_ = size
+        if init_video.dim() != 4:
+            raise ValueError(f'init_video must be uint8 frames [T, H0, W0, 3] or a float clip [3, T, H, W], got {tuple(init_video.shape)}')
+        if init_video.dtype == torch.uint8:
+            if init_video.shape[3] != 3 or init_video.shape[0] < frame_num:
+                raise ValueError(f'init_video: uint8 frames must be [T >= {frame_num}, H0, W0, 3], got {tuple(init_video.shape)}')
+            return ops.video_from_u8(init_video[:frame_num].to(self.device).contiguous(), H_, W_)
+        if not init_video.is_floating_point() or init_video.shape[0] != 3 or init_video.shape[1] < frame_num or tuple(init_video.shape[2:]) != (H_, W_):
+            raise ValueError(f'init_video: a float clip must be [3, T >= {frame_num}, {H_}, {W_}] (already at `size`), got {init_video.dtype} '
+                             f'{tuple(init_video.shape)}')
+        return init_video[:, :frame_num].to(self.device, torch.float32).contiguous()
+
+    def start_latent(self, init_video, size, frame_num, noise, sigma):
+        """the latent a video-to-video run starts from: (1 - sigma) z0 + sigma noise with z0 = vae.encode(init_clip(init_video)), one fused launch."""
+        z0 = self.vae.encode([self.init_clip(init_video, size, frame_num)])[0]
+        if tuple(z0.shape) != tuple(noise.shape):
+            raise ValueError(f'init_video encodes to {tuple(z0.shape)}, the latent of this call is {tuple(noise.shape)}')
+        # (also what makes the strength-1 start exact: 0 x finite = 0, and 0 + 1 x noise = noise)
+        assert torch.isfinite(z0).all().item(), 'the encoded init_video is not finite'
+        return ops.lincomb(torch.empty_like(noise), [(z0, 1.0 - sigma), (noise, sigma)])
+
     def generate(self, input_prompt, size=(1280, 720), frame_num=81, shift=5.0, sample_solver='unipc',
                  sampling_steps=50, guide_scale=5.0, n_prompt="", seed=-1, offload_model=True,
-                 noise=None, callback=None):
+                 noise=None, callback=None, init_video=None, strength=1.0):
+        """The reference's `generate` (text2video.py:114-271), plus a video-to-video start that is NOT part of the reference:
+
+        init_video: an existing clip to start from instead of pure noise — uint8 RGB frames [T, H0, W0, 3] of any size (tensor or array;
+            resized to cover `size` and centre-cropped on the GPU, ops.video_from_u8) or a float clip [3, T, H, W] in [-1, 1] already at
+            `size`; T >= frame_num, the first frame_num frames are used.
+        strength in (0, 1]: how much of the schedule runs (`v2v_steps`).  The clip is encoded (`vae.encode`, on every rank for itself: the
+            same bits everywhere, no collective), the start latent is (1 - sigma) z0 + sigma noise at the sigma of schedule index i0 and the
+            loop runs the steps i0 .. sampling_steps - 1; `callback(i, latent)` gets these schedule indices.  At strength 1 the start is
+            0 z0 + 1 noise: the result is bit-identical to the call without init_video and the same noise.
+        Without init_video nothing changes, call for call."""
+        n_run, i0 = v2v_steps(sampling_steps, strength)
+        if init_video is None and i0:
+            raise ValueError('strength < 1 needs init_video: there is nothing to start from')
         F = frame_num
         target_shape = (self.vae.model.z_dim, (F - 1) // self.vae_stride[0] + 1, size[1] // self.vae_stride[1],
                         size[0] // self.vae_stride[2])
@@ -145,11 +192,14 @@ class WanT2V:
                 raise NotImplementedError("Unsupported solver.")
 
             latent = noise
+            if init_video is not None:
+                sample_scheduler.set_begin_index(i0)
+                latent = self.start_latent(init_video, size, frame_num, noise, sample_scheduler.sigmas[i0].item() if i0 else 1.0)
             timesteps_host = timesteps.tolist()          # ONE sync for the whole loop
             if next(self.model.parameters()).device != self.device:     # only after a real offload (a no-op move would
                 self.model.to(self.device)                               # still drop the fused-weight views: 28 GB re-packed)
             noise_pred = torch.empty_like(latent)
-            for i, t_host in enumerate(timesteps_host):
+            for i, t_host in enumerate(timesteps_host[i0:], start=i0):
                 t = timesteps[i:i + 1]
                 pair = getattr(self.model, 'forward_pair', None)
                 if self.cfgp is None and pair is not None:

@@ -75,6 +75,14 @@ class FlowDPMSolverMultistepScheduler:
         self.lower_order_nums = 0
         self._step_index = None
 
+    def set_begin_index(self, begin_index=0):
+        """(the diffusers name) start `step` at schedule index `begin_index` instead of looking the first timestep up: a run that begins
+        in the middle of the schedule (WanT2V.generate with init_video).  The look-up takes the SECOND hit of a timestep that occurs
+        twice (the reference's rule): a start on the first of the two would skip a step.  Call after set_timesteps."""
+        if self.num_inference_steps is None or not 0 <= int(begin_index) < self.num_inference_steps:
+            raise ValueError(f'begin_index {begin_index} is outside the schedule: call set_timesteps first, then 0 <= begin_index < its length')
+        self._step_index = int(begin_index)
+
     def _init_step_index(self, timestep):
         t = int(timestep)
         hits = [i for i, v in enumerate(self._timesteps_host) if v == t]

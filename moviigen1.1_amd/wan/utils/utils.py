@@ -17,7 +17,7 @@ import torch
 
 from ..backend import ops
 
-__all__ = ['cache_video', 'cache_image', 'video_frames_uint8', 'str2bool']
+__all__ = ['cache_video', 'cache_image', 'video_frames_uint8', 'load_video', 'str2bool']
 
 
 def rand_name(length=8, suffix=''):
@@ -34,6 +34,30 @@ def video_frames_uint8(tensor, value_range=(-1, 1)):
             raise NotImplementedError('make_grid of several videos (nrow tiling) is not on the T2V path: one video per call')
         tensor = tensor[0]
     return ops.video_to_u8(tensor.to(torch.float32).contiguous(), min(value_range), max(value_range))
+
+
+def load_video(path):
+    """a clip from disk -> uint8 frames [T, H, W, 3] (numpy), what `WanT2V.generate(init_video=...)` takes.  A `.npy` file (the uint8
+    frames themselves, e.g. what cache_video writes when it has no video writer) always works; every other file type is decoded by
+    `imageio` when it is installed — this package has no video decoder of its own."""
+    if not osp.exists(path):
+        raise FileNotFoundError(f'load_video: {path} does not exist')
+    if osp.splitext(path)[1].lower() == '.npy':
+        frames = np.load(path, allow_pickle=False)
+    else:
+        try:
+            import imageio
+        except ModuleNotFoundError as e:
+            raise ImportError(f'load_video: reading {path} needs imageio, which is not installed; decode the clip elsewhere and pass '
+                              'its uint8 frames [T, H, W, 3] as a .npy file (numpy.save)') from e
+        reader = imageio.get_reader(path)
+        try:
+            frames = np.stack([np.asarray(fr) for fr in reader])
+        finally:
+            reader.close()
+    if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
+        raise ValueError(f'load_video: {path} holds {frames.dtype} {frames.shape}, expected uint8 RGB frames [T, H, W, 3]')
+    return np.ascontiguousarray(frames)
 
 
 def cache_video(tensor, save_file=None, fps=30, suffix='.mp4', nrow=8, normalize=True, value_range=(-1, 1), retry=5):

@@ -10,7 +10,8 @@ file naming (generate.py:300-306), on the MI355X engine.
 Differences: no xfuser (sequence parallelism is built in; `--ulysses_size U` x `--ring_size R`
 must equal the world size as in the reference), `--use_prompt_extend` is not built and says so,
 `--t5_fsdp` / `--t5_cpu` are accepted (the 9.4 GB encoder is simply replicated on the GPU).  Extra:
-`--cfg_parallel`, `--vae_parallel` (this engine's multi-GPU layouts) and
+`--cfg_parallel`, `--vae_parallel` (this engine's multi-GPU layouts),
+`--init_video FILE` / `--strength F` (a video-to-video start, `WanT2V.generate(init_video=, strength=)`) and
 `--prompt_embeds FILE` (a torch file {'prompt': [len,4096], 'negative': [len,4096]} instead of running
 umT5 — for boxes without the tokenizer files)."""
 import argparse
@@ -30,7 +31,7 @@ sys.path.insert(0, os.path.join(ROOT, 'moviigen1.1_amd'))
 
 import wan  # noqa: E402
 from wan.configs import SIZE_CONFIGS, SUPPORTED_SIZES, WAN_CONFIGS  # noqa: E402
-from wan.utils.utils import cache_image, cache_video, str2bool  # noqa: E402
+from wan.utils.utils import cache_image, cache_video, load_video, str2bool  # noqa: E402
 
 EXAMPLE_PROMPT = {   # one short default per task (the reference ships long showcase prompts here)
     't2v-14B': {'prompt': 'A cat walks on the grass, realistic style.'},
@@ -69,6 +70,10 @@ FLAGS = [
                                  'pipeline = the decoder layers cut into one segment per rank.')),
     ('--dit_gemm', dict(type=str, default='bf16', choices=['bf16', 'mxfp8'],
                         help="arithmetic of the six per-block DiT linears: bf16 (the reference's) or mxfp8 (opt-in, block-scaled fp8 MFMA; not with --dit_fsdp).")),
+    ('--init_video', dict(type=str, default=None,
+                          help='video-to-video: start from this clip instead of pure noise (uint8 frames [T,H,W,3] as .npy, or any file imageio reads when it '
+                               'is installed); resized to cover --size and centre-cropped. Not part of the reference CLI.')),
+    ('--strength', dict(type=float, default=1.0, help='with --init_video: the fraction of the sampling schedule that runs, in (0, 1]; 1 = from pure noise.')),
     ('--prompt_embeds', dict(type=str, default=None, help="torch file {'prompt','negative'} of umT5 embeddings, replaces the text encoder.")),
 ]
 
@@ -86,6 +91,8 @@ def _validate_args(args):
     if 't2i' in args.task:
         assert args.frame_num == 1, f'Unsupport frame_num {args.frame_num} for task {args.task}'
     args.base_seed = args.base_seed if args.base_seed >= 0 else random.randint(0, sys.maxsize)
+    assert 0.0 < args.strength <= 1.0, f'--strength must be in (0, 1], got {args.strength}'
+    assert args.init_video is not None or args.strength == 1.0, '--strength needs --init_video'
     assert args.size in SUPPORTED_SIZES[args.task], \
         f"Unsupport size {args.size} for task {args.task}, supported sizes are: {', '.join(SUPPORTED_SIZES[args.task])}"
 
@@ -162,10 +169,14 @@ def generate(args):
         emb = torch.load(args.prompt_embeds, map_location='cpu', weights_only=True)
         prompt, n_prompt = emb['prompt'], emb['negative']
     logging.info(f"Generating {'image' if 't2i' in args.task else 'video'} ...")
+    v2v = {}
+    if args.init_video:         # every rank reads the file and encodes the clip for itself
+        v2v = dict(init_video=load_video(args.init_video), strength=args.strength)
+        logging.info(f"video-to-video start from {args.init_video}: {v2v['init_video'].shape[0]} frames, strength {args.strength}")
     video = pipe.generate(prompt, size=SIZE_CONFIGS[args.size], frame_num=args.frame_num, shift=args.sample_shift,
                           sample_solver=args.sample_solver, sampling_steps=args.sample_steps,
                           guide_scale=args.sample_guide_scale, n_prompt=n_prompt, seed=args.base_seed,
-                          offload_model=args.offload_model)
+                          offload_model=args.offload_model, **v2v)
     if rank == 0:
         if args.save_file is None:
             args.save_file = default_save_name(args)

@@ -4,7 +4,8 @@ Synthetic weights of the shipped decoder shape (dim 96), z = randn seed 7 (SURVE
     python tools/bench_vae.py --chunk 4 --encode [--stages]
 also times WanVAE.encode of a [3,81,832,1920] and a [3,81,720,1280] clip (median of --encode-reps calls, events around the whole
 call) behind the decode leg of the same run: seconds, executed TFLOP/s against the same fp32-MFMA peak, peak memory; with --stages
-the milliseconds and TFLOP/s of every encoder stage."""
+the milliseconds and TFLOP/s of every encoder stage; --mode bf16x3 times the encode of a bf16x3 object; the frame ingest (mg_video_from_u8,
+1080p -> 1920x832x81) is timed behind it."""
 import argparse
 import json
 import os
@@ -86,7 +87,7 @@ if args.encode:
             secs.append(a.elapsed_time(b) / 1e3)
         med = sorted(secs)[len(secs) // 2]
         ef = vae_encode_flops(81, eh, ew)
-        print(json.dumps({'metric': 'vae_encode_sec', 'value': med, 'all_sec': secs, 'size': f'{ew}x{eh}', 'frames': 81, 'latent': list(lat.shape),
+        print(json.dumps({'metric': 'vae_encode_sec', 'value': med, 'all_sec': secs, 'mode': args.mode, 'size': f'{ew}x{eh}', 'frames': 81, 'latent': list(lat.shape),
                           'pflop': ef / 1e15, 'tflops_fp32': ef / med / 1e12, 'fp32_mfma_peak_tflops': 157.3, 'frac': ef / med / 157.3e12,
                           'decode_frac_same_run': decode_frac, 'finite': bool(torch.isfinite(lat).all().item()),
                           'peak_mem_gb': torch.cuda.max_memory_allocated() / 2**30, 'of_which_clip_and_weights_gb': base_mem / 2**30}))
@@ -120,6 +121,31 @@ if args.encode:
             fr = sf['encoder.conv1'] + sf['encoder.head']
             print(f"{'video_in + encoder.conv1 + encoder.head':40s} {rest:9.1f} {fr / 1e12:7.1f} {fr / rest / 1e9:9.1f} {fr / rest / 1e9 / 157.3:10.2f}")
         del clip, lat
+
+if args.encode:
+    # the way in of a video-to-video start: 81 uint8 frames -> the [3,81,832,1920] fp32 clip (mg_video_from_u8).  1920x1080: cover = the same width,
+    # 124 rows cropped top and bottom, every output has the weights {1, 0} per axis; 3840x2160: 2x down, 5 taps per axis, then the same crop.
+    # Bytes: the input rows the crop keeps are read once from HBM, the clip is written once.
+    from wan.backend import ops
+    clip = torch.empty(3, 81, 832, 1920, device=dev)
+    for (h0, w0) in ((1080, 1920), (2160, 3840)):
+        frames = torch.randint(0, 256, (81, h0, w0, 3), dtype=torch.uint8, device=dev, generator=torch.Generator(device=dev).manual_seed(3))
+        ops.video_from_u8(frames, 832, 1920, out=clip)
+        ms = []
+        for _ in range(5):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            ops.video_from_u8(frames, 832, 1920, out=clip)
+            b.record()
+            torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b))
+        med = sorted(ms)[len(ms) // 2]
+        kept = 81 * (832 * h0 // 1080) * w0 * 3
+        print(json.dumps({'metric': 'video_from_u8_ms', 'value': med, 'all_ms': ms, 'from': f'{w0}x{h0}x81 uint8', 'to': '1920x832x81 fp32',
+                          'bytes_read_kept_rows': kept, 'bytes_written': clip.numel() * 4, 'gb_per_s': (kept + clip.numel() * 4) / med / 1e6,
+                          'finite': bool(torch.isfinite(clip).all().item())}))
+        del frames
+    del clip
 
 if args.bands:
     # one rank of P, emulated: what the W split costs a rank in kernels and copies (measured) and in link time (bytes / rate, not overlapped)
