@@ -473,6 +473,26 @@ int mg_vae_video_in_f32(const float* video, int T, int H, int W, int t0, int n, 
 int mg_vae_latent_out_f32(const float* x, int ldx, const float* mean, const float* inv_std, int C, int T, int H, int W, float* out,
                           void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * LoRA adapters (WanModel.load_lora).  A pure addition to ABI 9.
+ * ---------------------------------------------------------------------------------------- */
+
+/* Low-rank update of a weight matrix, in place (no reference counterpart):
+ *   w[n][k] <- round_w( w[n][k] + sum_{j<R} up[n][j] * down[j][k] )
+ * w [N][K] bf16 (w_f32 = 0) or fp32 (w_f32 = 1), row stride ldw elements;
+ * up [N][R] fp32 (row stride ldu), down [R][K] fp32 (row stride ldd).
+ * The old weight is widened to fp32 and the R products are added to it one after the other, in order of j, each by one fp32 fma (the
+ * exact-f32 MFMA); bf16 storage then takes ONE round-to-nearest-even, fp32 storage the sum as it is.  (IEEE addition: a weight of -0
+ * whose update is 0 is stored as +0.)  The caller folds an adapter's scale into `up` and passes several adapters as one pair of
+ * factors concatenated along R; any R >= 1 is taken, in chunks, with no padding asked of the caller.
+ * N >= 1, K >= 8 and K % 8 == 0, ldw >= K.  Elements of a row past K and rows outside [0, N) of a taller buffer are never written: a
+ * row slice or a column view of a larger matrix is merged through its own pointer.  Every element of w is read and written by one
+ * lane, as part of a 16-byte vector; no atomics.
+ * MG_ERR_ARG: a null pointer, w not 16-byte aligned, K % 8 != 0, R, N or K < 1, w_f32 not 0 / 1.
+ * MG_ERR_SHAPE: ldw < K or ldw not a multiple of 16 bytes, ldu < R, ldd < K, a factor not 4-byte aligned. */
+int mg_lora_merge(void* w, int w_f32, int64_t ldw, int N, int K, const float* up, int64_t ldu, const float* down, int64_t ldd, int R,
+                  void* stream);
+
 #ifdef MG_AB_BUILD
 /* ------------------------------------------------------------------------------------------
  * A/B LIBRARY ONLY (libmoviigen_hip_ab.so, built from the same sources with -DMG_AB_BUILD; the product library

@@ -246,6 +246,22 @@ def lincomb(out, terms):
     return out
 
 
+def lora_merge(w, up, down):
+    """w [N, K] bf16 or fp32, IN PLACE: w <- round(w + up [N, R] fp32 @ down [R, K] fp32), fp32 products and sums, one rounding for
+    bf16 storage (include/moviigen_hip.h).  w may be a row slice or a column view of a larger matrix (row stride free, a multiple of
+    16 bytes): nothing outside [N, K] is written."""
+    if not torch.is_tensor(w) or w.dtype not in (torch.bfloat16, torch.float32):
+        raise lib.MoviigenHipError(f'w: expected a bf16 or fp32 tensor, got {getattr(w, "dtype", type(w))}')
+    _chk(w, w.dtype, 'w'); _chk(up, torch.float32, 'up'); _chk(down, torch.float32, 'down')
+    if w.dim() != 2 or up.dim() != 2 or down.dim() != 2 or up.shape[0] != w.shape[0] or down.shape[1] != w.shape[1] \
+            or up.shape[1] != down.shape[0]:
+        raise lib.MoviigenHipError(f'lora_merge shape mismatch w{tuple(w.shape)} up{tuple(up.shape)} down{tuple(down.shape)}')
+    N, K = w.shape
+    lib.call('mg_lora_merge', _p(w), int(w.dtype == torch.float32), w.stride(0), N, K, _p(up), up.stride(0), _p(down),
+             down.stride(0), up.shape[1], _st())
+    return w
+
+
 def cfg_combine(out, uncond, cond, g):
     _chk(uncond, torch.float32, 'uncond'); _chk(cond, torch.float32, 'cond')
     lib.call('mg_cfg_combine_f32', _p(out), _p(uncond), _p(cond), float(g), out.numel(), _st())

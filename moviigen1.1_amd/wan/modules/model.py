@@ -260,6 +260,8 @@ class WanModel(nn.Module):
         self._ws = {}
         self._rope = {}
         self._ctx_cache = {}
+        self._lora = []                 # load_lora: (name, strength) of the adapters merged into the weights
+        self._lora_base = None          # ... and the touched weights as they were (keep_base=True), for unload_lora
 
     @property
     def freqs(self):
@@ -346,9 +348,84 @@ class WanModel(nn.Module):
             want = torch.bfloat16 if name.endswith(_BF16_SUFFIXES) else torch.float32
             if p.dtype != want:
                 p.data = p.data.to(want)
+        if self._lora_base:             # the kept base weights follow the parameters (device moves; a cast and back is exact)
+            self._lora_base = {k: fn(v) for k, v in self._lora_base.items()}
         self._invalidate()
         self._ws, self._rope = {}, {}
         return out
+
+    # ------------------------------------------------------------------------------------------
+    # LoRA adapters: merged into the weights on the device, once per model (DESIGN.md §3.6)
+    # ------------------------------------------------------------------------------------------
+    @property
+    def lora(self):
+        """[(adapter file name or '<dict>', strength)] of the adapters currently merged into the weights; [] = the base weights"""
+        return list(self._lora)
+
+    def lora_targets(self):
+        """{module name: weight} of every linear layer an adapter may name (`blocks.3.cross_attn.k`, `blocks.0.ffn.2`, `text_embedding.0`,
+        `time_projection.1`, `head.head`, ...): bf16 storage, or fp32 for the time embedding / projection and the head.  patch_embedding
+        is a convolution and is not among them."""
+        return {n: m.weight for n, m in self.named_modules() if isinstance(m, _Lin)}
+
+    @torch.no_grad()
+    def load_lora(self, adapters, strength=1.0, keep_base=True, strict=True):
+        """Merge LoRA adapters into the weights, in place, on the device: per target W <- round(W + sum_a s_a * up_a @ down_a), s_a =
+        strength_a * alpha_a / rank_a (strength_a where the file has no alpha).  adapters: one `.safetensors` path or dict of tensors, or
+        a list of them (wan/utils/lora.py: the spellings read); strength: one float, or one per adapter.  The scaled factors of ALL
+        adapters are concatenated along the rank and merged by ONE mg_lora_merge per weight, in fp32 with a single rounding to the
+        weight's storage type — N adapters cost one rounding, not N.  Nothing else changes: the next forward re-packs, re-quantises
+        the 'mxfp8' weights and recomputes the cached cross-attention k|v, and from then on runs exactly what it would run on a
+        checkpoint that held these weights.  keep_base: clone the touched weights first (unload_lora restores them bit for bit)."""
+        from ..utils.lora import read_lora
+        targets = self.lora_targets()
+        dev = self.patch_embedding.weight.device
+        if dev.type != 'cuda':
+            raise RuntimeError('WanModel.load_lora needs the model on a HIP device (model.to("cuda")): the merge is a HIP kernel '
+                               'and has no CPU implementation')
+        if self._lora:
+            raise RuntimeError(f'adapters {self._lora} are merged into the weights already: unload_lora() first')
+        if getattr(self, '_shards', None) is not None:
+            raise NotImplementedError('load_lora needs resident weights: merge before the weights are block-sharded '
+                                      '(wan.distributed.fsdp shard_model; WanT2V(lora=...) does it in that order)')
+        if isinstance(adapters, (str, os.PathLike, dict)):
+            adapters = [adapters]
+        adapters = list(adapters)
+        strengths = [float(strength)] * len(adapters) if isinstance(strength, (int, float)) else [float(s) for s in strength]
+        if len(strengths) != len(adapters):
+            raise ValueError(f'{len(adapters)} adapters but {len(strengths)} strengths')
+        shapes = {n: tuple(w.shape) for n, w in targets.items()}
+        factors = {}                    # target -> [(up, down, scale)]
+        for src, s in zip(adapters, strengths):
+            for name, (up, down, alpha) in read_lora(src, shapes, strict=strict).items():
+                factors.setdefault(name, []).append((up, down, s if alpha is None else s * alpha / up.shape[1]))
+        if keep_base:
+            self._lora_base = {n: targets[n].data.clone() for n in factors}
+        for name, fs in factors.items():
+            ups = []
+            for up, _, scale in fs:     # the scale is folded into `up` in fp32, by the engine's own kernel
+                up = up.to(dev)
+                ups.append(ops.lincomb(torch.empty_like(up), [(up, scale)]))
+            downs = [down.to(dev) for _, down, _ in fs]
+            ops.lora_merge(targets[name].data, ups[0] if len(ups) == 1 else torch.cat(ups, 1),
+                           downs[0] if len(downs) == 1 else torch.cat(downs, 0))
+        self._lora = [(src if isinstance(src, (str, os.PathLike)) else '<dict>', s) for src, s in zip(adapters, strengths)]
+        self._invalidate()
+        return self
+
+    @torch.no_grad()
+    def unload_lora(self):
+        """copy the base weights back (load_lora(keep_base=True)): state_dict() is then bit-identical to before load_lora"""
+        if not self._lora:
+            raise RuntimeError('no adapters are loaded')
+        if self._lora_base is None:
+            raise RuntimeError('the adapters were loaded with keep_base=False: the base weights were not kept, reload the checkpoint')
+        targets = self.lora_targets()
+        for name, base in self._lora_base.items():
+            targets[name].data.copy_(base)      # in place: q / k / v stay views of the fused storage
+        self._lora, self._lora_base = [], None
+        self._invalidate()
+        return self
 
     # ------------------------------------------------------------------------------------------
     # engine-side packing: fused QKV / cross-KV weights, stacked modulation

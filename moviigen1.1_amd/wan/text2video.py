@@ -40,7 +40,7 @@ class WanT2V:
 
     def __init__(self, config, checkpoint_dir, device_id=0, rank=0, t5_fsdp=False, dit_fsdp=False, use_usp=False,
                  t5_cpu=False, text_encoder=None, model=None, vae=None, cfg_parallel=False, vae_parallel=False, use_ring=False, sp_degrees=None,
-                 dit_gemm='bf16'):
+                 dit_gemm='bf16', lora=None, lora_strength=1.0):
         self.device = torch.device(f'cuda:{device_id}')
         self.config = config
         self.rank = rank
@@ -68,6 +68,10 @@ class WanT2V:
         if dist.is_initialized():
             dist.barrier()
         self.model.to(self.device)
+        # LoRA adapters (one `.safetensors` path / dict of tensors or a list, one strength or one per adapter) are merged into the resident
+        # weights here: before they are block-sharded and before 'mxfp8' quantises them (WanModel.load_lora).  None touches nothing
+        if lora is not None:
+            self.model.load_lora(lora, strength=lora_strength)
         self.cfgp = None
         self.vae_parallel = bool(vae_parallel) and dist.is_initialized() and dist.get_world_size() > 1
         # vae_parallel: True / 'spatial' = every rank decodes its band of image columns (WanVAE.decode_spatial); 'pipeline' = the layer pipeline

@@ -11,7 +11,8 @@ Differences: no xfuser (sequence parallelism is built in; `--ulysses_size U` x `
 must equal the world size as in the reference), `--use_prompt_extend` is not built and says so,
 `--t5_fsdp` / `--t5_cpu` are accepted (the 9.4 GB encoder is simply replicated on the GPU).  Extra:
 `--cfg_parallel`, `--vae_parallel` (this engine's multi-GPU layouts),
-`--init_video FILE` / `--strength F` (a video-to-video start, `WanT2V.generate(init_video=, strength=)`) and
+`--init_video FILE` / `--strength F` (a video-to-video start, `WanT2V.generate(init_video=, strength=)`),
+`--lora PATH[:STRENGTH]` (repeatable: LoRA adapters merged into the DiT weights on the device, `WanModel.load_lora`) and
 `--prompt_embeds FILE` (a torch file {'prompt': [len,4096], 'negative': [len,4096]} instead of running
 umT5 — for boxes without the tokenizer files)."""
 import argparse
@@ -74,8 +75,23 @@ FLAGS = [
                           help='video-to-video: start from this clip instead of pure noise (uint8 frames [T,H,W,3] as .npy, or any file imageio reads when it '
                                'is installed); resized to cover --size and centre-cropped. Not part of the reference CLI.')),
     ('--strength', dict(type=float, default=1.0, help='with --init_video: the fraction of the sampling schedule that runs, in (0, 1]; 1 = from pure noise.')),
+    ('--lora', dict(type=str, action='append', default=None, metavar='PATH[:STRENGTH]',
+                    help='a LoRA adapter (.safetensors: PEFT / diffusers or kohya / ComfyUI key names) merged into the DiT weights before sampling, '
+                         'with an optional strength (default 1.0); may be given several times: all adapters are merged in one step, with one rounding.')),
     ('--prompt_embeds', dict(type=str, default=None, help="torch file {'prompt','negative'} of umT5 embeddings, replaces the text encoder.")),
 ]
+
+
+def _lora_arg(arg):
+    """'PATH' or 'PATH:STRENGTH' -> (path, strength).  Only a suffix that reads as a number is a strength: 'C:\\a.safetensors' and
+    'dir:x/a.safetensors' are paths."""
+    path, sep, tail = arg.rpartition(':')
+    if sep and path:
+        try:
+            return path, float(tail)
+        except ValueError:
+            pass
+    return arg, 1.0
 
 
 def _validate_args(args):
@@ -93,6 +109,7 @@ def _validate_args(args):
     args.base_seed = args.base_seed if args.base_seed >= 0 else random.randint(0, sys.maxsize)
     assert 0.0 < args.strength <= 1.0, f'--strength must be in (0, 1], got {args.strength}'
     assert args.init_video is not None or args.strength == 1.0, '--strength needs --init_video'
+    args.lora = [_lora_arg(a) for a in args.lora or []]
     assert args.size in SUPPORTED_SIZES[args.task], \
         f"Unsupport size {args.size} for task {args.task}, supported sizes are: {', '.join(SUPPORTED_SIZES[args.task])}"
 
@@ -163,6 +180,7 @@ def generate(args):
     pipe = wan.WanT2V(config=cfg, checkpoint_dir=args.ckpt_dir, device_id=local, rank=rank, t5_fsdp=args.t5_fsdp,
                       dit_fsdp=args.dit_fsdp, use_usp=(args.ulysses_size > 1 or args.ring_size > 1), t5_cpu=args.t5_cpu,
                       cfg_parallel=args.cfg_parallel, vae_parallel=args.vae_parallel, dit_gemm=args.dit_gemm,
+                      lora=[p for p, _ in args.lora] or None, lora_strength=[s for _, s in args.lora] or 1.0,
                       sp_degrees=(args.ulysses_size, args.ring_size) if args.ring_size > 1 else None)
     prompt, n_prompt = args.prompt, ''
     if args.prompt_embeds:
