@@ -46,8 +46,6 @@
 #define M16_K(slot) ((slot) * M16_TILE)
 #define M16_V(slot) (3 * M16_TILE + (slot) * M16_TILE)
 
-typedef const __attribute__((address_space(1))) void* m16_gptr_t;
-typedef __attribute__((address_space(3))) void* m16_lptr_t;
 MG_DEV bf16x8_t m16_bf(u32x4_t v) { return __builtin_bit_cast(bf16x8_t, v); }
 struct M16State {
     f32x4_t ot[8][4];      // O^T [d block][query block]             (AGPRs: builtin MFMAs)
@@ -473,7 +471,7 @@ __global__ __launch_bounds__(M16_THREADS, 1) void attn_hd128_m16_kernel(
     // LDS-DMA: a tile is 16 pieces of 1 KiB; wave w moves pieces 4w..4w+3 of the K tile and of the V tile
     const int nfull = last_lim == 64 ? T : T - 1;
     // tile indices past the end are clamped (a redundant reload of the last tile into a free slot) instead of guarded
-    const unsigned lds0 = (unsigned)(uintptr_t)(m16_lptr_t)smem;
+    const unsigned lds0 = (unsigned)(uintptr_t)(mg_lptr_t)smem;
     // (round 6) EVERY LDS-DMA piece of the kernel is a buffer load behind the head's K / V resource: per-lane offset `dvo` (ONE register, the same for all
     // pieces), the tile's byte offset a scalar, the LDS destination in M0, the pieces' 1 KiB steps in the instruction offset (global and LDS side alike).  The
     // global_load_lds form this replaces outside the steady loop needed a 64-bit per-lane address per piece: the compiler hoisted those out of the item loop,
@@ -867,11 +865,8 @@ void mg_attn_m16_hooks(int dbg, unsigned long long* prof, unsigned* flagcnt) { g
 int mg_attn_m16_launch(const uint16_t* q, int64_t ldq, const uint16_t* kp, const uint16_t* vp, uint16_t* o, int64_t ldo,
                        int64_t Lq, int64_t Lk, int heads, float c_log2, int prescaled, int nqb, float* lse, int reserve_cus,
                        unsigned* workspace, hipStream_t st) {
-    int n_cu = mg_cu_count();
+    const int n_cu = mg_persistent_cus(reserve_cus);    // one workgroup per CU (96 KiB LDS), a multiple of the 8 XCDs
     if (n_cu < 0) return MG_ERR_LAUNCH;
-    n_cu &= ~7;                                         // one workgroup per CU (96 KiB LDS), a multiple of the 8 XCDs
-    n_cu -= (reserve_cus + 7) & ~7;
-    if (n_cu < 8) n_cu = 8;
     const int total = nqb * heads;
     const unsigned grid = total <= n_cu ? (unsigned)total : (unsigned)n_cu;   // persistent when there is more work than CUs
     // Items by ticket from 32 rounds on (the metric's launch has 80: +1.35 %, 220.3 against 223.3 ms; 16 rounds: -0.2 %, and at the 10 rounds of

@@ -32,10 +32,7 @@
 #define W64_K(slot) ((slot) * W64_TILE)
 #define W64_V(slot) (3 * W64_TILE + (slot) * W64_TILE)
 
-typedef const __attribute__((address_space(1))) void* w64_gptr_t;
-typedef __attribute__((address_space(3))) void* w64_lptr_t;
 MG_DEV bf16x8_t w64_bf(u32x4_t v) { return __builtin_bit_cast(bf16x8_t, v); }
-MG_DEV void w64_glds16(const void* g, void* l) { __builtin_amdgcn_global_load_lds((w64_gptr_t)g, (w64_lptr_t)l, 16, 0, 0); }
 
 struct W64State {
     f32x16_t ot[4][2];     // O^T [d block][query block]
@@ -312,14 +309,14 @@ __global__ __launch_bounds__(W64_THREADS, 1) void attn_hd128_w64_kernel(
     // instead of guarded: no branch per piece in the hot loop.  (The SADDR form of the LDS-DMA — SGPR
     // base + 32-bit lane offset + immediate, hand-written — was measured: 139 cycles per piece instead
     // of 55 with hipcc's 64-bit per-lane address form.)
-    const unsigned lds0 = (unsigned)(uintptr_t)(w64_lptr_t)smem;
+    const unsigned lds0 = (unsigned)(uintptr_t)(mg_lptr_t)smem;
     auto dma_k = [&](int t, int slot, int n) __attribute__((always_inline)) {
         const int tt = t < T ? t : T - 1;
-        w64_glds16(k_src + ((int64_t)phys(tt) * 16384 + n * 1024) + lane_off, smem + W64_K(slot) + wave * 4096 + n * 1024);
+        mg_glds16(k_src + ((int64_t)phys(tt) * 16384 + n * 1024) + lane_off, smem + W64_K(slot) + wave * 4096 + n * 1024);
     };
     auto dma_v = [&](int t, int slot, int n) __attribute__((always_inline)) {
         const int tt = t < T ? t : T - 1;
-        w64_glds16(v_src + ((int64_t)phys(tt) * 16384 + n * 1024) + lane_off, smem + W64_V(slot) + wave * 4096 + n * 1024);
+        mg_glds16(v_src + ((int64_t)phys(tt) * 16384 + n * 1024) + lane_off, smem + W64_V(slot) + wave * 4096 + n * 1024);
     };
     const int kperm = (l31 & 0x13) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);
     const unsigned kbase = lds0 + g * 1024 + kperm * 16;               // + W64_K(slot) + kb*512 + kk*2048
@@ -520,10 +517,8 @@ extern "C" void mg_attn_w64_flag_counter(unsigned* dev_counter) { g_w64_flagcnt 
 
 int mg_attn_w64_launch(const uint16_t* q, int64_t ldq, const uint16_t* kp, const uint16_t* vp, uint16_t* o, int64_t ldo,
                        int64_t Lq, int64_t Lk, int heads, float c_log2, int nqb, float* lse, hipStream_t st) {
-    int n_cu = mg_cu_count();
+    const int n_cu = mg_persistent_cus();               // one workgroup per CU (96 KiB LDS), a multiple of the 8 XCDs
     if (n_cu < 0) return MG_ERR_LAUNCH;
-    n_cu &= ~7;                                         // one workgroup per CU (96 KiB LDS), a multiple of the 8 XCDs
-    if (n_cu < 8) n_cu = 8;
     const int total = nqb * heads;
     const unsigned grid = total <= n_cu ? (unsigned)total : (unsigned)n_cu;   // persistent when there is more work than CUs
     if (g_w64_prof)

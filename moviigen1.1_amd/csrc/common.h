@@ -68,6 +68,13 @@ MG_DEV float gelu_tanh(float x) {
 }
 MG_DEV float silu(float x) { return x / (1.f + __expf(-x)); }
 
+// LDS-DMA (global_load_lds_dwordx4 / _dword): 16 or 4 bytes per lane from g straight to LDS at l + size * lane, no VGPR round trip.
+// (mg_lptr_t)p is also how a kernel gets the 32-bit LDS address of p for its inline-assembly ds_read.
+typedef const __attribute__((address_space(1))) void* mg_gptr_t;
+typedef __attribute__((address_space(3))) void* mg_lptr_t;
+MG_DEV void mg_glds16(const void* g, void* l) { __builtin_amdgcn_global_load_lds((mg_gptr_t)g, (mg_lptr_t)l, 16, 0, 0); }
+MG_DEV void mg_glds4(const void* g, void* l) { __builtin_amdgcn_global_load_lds((mg_gptr_t)g, (mg_lptr_t)l, 4, 0, 0); }
+
 // CUs of the CURRENT device, asked per call (an attribute lookup; a function-static cache would be wrong in a process
 // that drives devices of different sizes and racy on first use from two threads); -1 on error
 static inline int mg_cu_count() {
@@ -76,6 +83,14 @@ static inline int mg_cu_count() {
         hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
         return -1;
     return n;
+}
+// CUs a persistent launch may occupy — one workgroup per CU, dealt round-robin over the 8 XCDs: the device's count rounded down to a
+// multiple of 8, less `reserve_cus` (rounded up to one: CUs left free for a kernel on another stream), at least 8; -1 on error
+static inline int mg_persistent_cus(int reserve_cus = 0) {
+    int n_cu = mg_cu_count();
+    if (n_cu < 0) return -1;
+    n_cu = (n_cu & ~7) - ((reserve_cus + 7) & ~7);
+    return n_cu < 8 ? 8 : n_cu;
 }
 
 static inline int mg_check_launch() {

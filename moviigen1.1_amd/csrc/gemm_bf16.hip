@@ -19,22 +19,15 @@
 //    (bias, GELU, gate, fp32 residual read-modify-write) is row-local with 8/16-byte accesses.
 //  * workgroup ids are remapped so each XCD (private 4 MiB L2) walks a contiguous, 8-tile-tall
 //    band of the output: the concurrently resident tiles of one XCD share A and W panels.
-#include "common.h"
 #include "gemm_epilogue.h"
-#include "../../include/moviigen_hip.h"
+#include "gemm_launch.h"
+#include "gemm_raster.h"
 
 #define BM 128
 #define BN 128
 #define BK 64
 #define GEMM_THREADS 256
 #define TILE_BYTES (128 * BK * 2)  // 16 KiB per operand tile
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-MG_DEV void glds16(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)l, 16, 0, 0);
-}
 
 template <int EPI>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bf16_kernel(
@@ -43,10 +36,11 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bf16_kernel(
     const float* __restrict__ gate, int tiles_m, int tiles_n) {
     __shared__ __attribute__((aligned(16))) char smem[4 * TILE_BYTES];  // [buf][A|W]
 
-    // ---- workgroup -> tile: XCD-contiguous remap, then 8-tall grouped raster --------------
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    // ---- workgroup -> tile: XCD-contiguous remap (gemm_raster.h: the XCD split of the GRID), then 8-tall grouped raster --------------
+    const int bid = blockIdx.x;
+    int xcd_first, xcd_count;
+    mg_xcd_range(gridDim.x, bid & 7, xcd_first, xcd_count);
+    const int swz = xcd_first + (bid >> 3);
     const int GM = 8;
     const int per_group = GM * tiles_n;
     const int group = swz / per_group;
@@ -85,8 +79,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bf16_kernel(
         const int koff = kt * BK;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            glds16(ga[i] + koff, la + i * 8 * 128);
-            glds16(gw[i] + koff, lw + i * 8 * 128);
+            mg_glds16(ga[i] + koff, la + i * 8 * 128);
+            mg_glds16(gw[i] + koff, lw + i * 8 * 128);
         }
     };
 
@@ -134,11 +128,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bf16_kernel(
     mg_gemm_epilogue<EPI, 2, 2>(acc, m0 + wm * 64, n0 + wn * 64, l31, g, M, N, bias, gate, out, ldo);
 }
 
-int mg_gemm_v12_launch(const uint16_t* A, int64_t lda, const uint16_t* Wt, int64_t ldw, const float* bias, int64_t M,
-                       int N, int K, int epilogue, void* out, int64_t ldo, const float* gate, hipStream_t st);       // gemm_bf16_v12.hip
-int mg_gemm_v2_launch(const uint16_t* A, int64_t lda, const uint16_t* Wt, int64_t ldw, const float* bias, int64_t M,
-                      int N, int K, int epilogue, void* out, int64_t ldo, const float* gate, hipStream_t st);
-
 // Tile schedules in the PRODUCT library (libmoviigen_hip.so), chosen by shape alone — no switch, no process-global state:
 //   12 = 256x256x64 tile, 16x16x32 MFMA, one wave per SIMD, persistent, loads two k-tiles ahead (gemm_bf16_v12.hip): M > 256 and N > 128;
 //    2 = 256x128x64, 8 waves, 3 stages (gemm_bf16_v2.hip): everything narrower, and what variant 12's launcher hands back (one k-tile,
@@ -148,17 +137,9 @@ int mg_gemm_v2_launch(const uint16_t* A, int64_t lda, const uint16_t* Wt, int64_
 // compiler-scheduled) — behind mg_gemm_set_variant, a process-global MEASUREMENT switch, and the s_memtime hooks.  Archived under
 // experiments/: 3, 4, 5, 6, 9, 10.
 #ifdef MG_AB_BUILD
-int mg_gemm_v7_launch(const uint16_t* A, int64_t lda, const uint16_t* Wt, int64_t ldw, const float* bias, int64_t M,
-                      int N, int K, int epilogue, void* out, int64_t ldo, const float* gate, hipStream_t st);
-int mg_gemm_v8_launch(const uint16_t* A, int64_t lda, const uint16_t* Wt, int64_t ldw, const float* bias, int64_t M,
-                      int N, int K, int epilogue, void* out, int64_t ldo, const float* gate, hipStream_t st);
-int mg_gemm_v11_launch(const uint16_t* A, int64_t lda, const uint16_t* Wt, int64_t ldw, const float* bias, int64_t M,
-                       int N, int K, int epilogue, void* out, int64_t ldo, const float* gate, hipStream_t st);
 unsigned long long* g_gemm5_prof = nullptr;   // s_memtime hook of the 256x256 kernels (7, 8, 11, 12)
 extern "C" void mg_gemm5_debug_profile(unsigned long long* dev_buf) { g_gemm5_prof = dev_buf; }
 static int g_gemm_variant = 0;   // 0 = the product's rule
-void mg_gemm_v11_set_flags(int f);
-void mg_gemm_v12_set_flags(int f);
 extern "C" int mg_gemm_set_variant(int v) {      // 110 + f / 200 + f: variant 11 / 12 with measurement flags f (gemm_bf16_v11.hip, gemm_bf16_v12.hip)
     const int base = v >= 200 ? 12 : v >= 110 ? 11 : v;
     if (base != 0 && base != 1 && base != 2 && base != 7 && base != 8 && base != 11 && base != 12) return MG_ERR_ARG;      // no silent aliases
@@ -174,12 +155,10 @@ extern "C" int mg_gemm_set_variant(int v) {      // 110 + f / 200 + f: variant 1
 extern "C" int mg_gemm_bf16(const uint16_t* A, int64_t lda, const uint16_t* Wt, int64_t ldw,
                             const float* bias, int64_t M, int N, int K, int epilogue, void* out,
                             int64_t ldo, const float* gate, void* stream) {
-    if (!A || !Wt || !out) return MG_ERR_ARG;
-    if (epilogue < 0 || epilogue > 3) return MG_ERR_ARG;
-    if (M < 0 || N <= 0 || K <= 0 || (K % BK) || (lda & 7) || (ldw & 7) || (ldo & 3)) return MG_ERR_SHAPE;
-    if (((uintptr_t)A & 15) || ((uintptr_t)Wt & 15) || ((uintptr_t)out & 15)) return MG_ERR_SHAPE;
-    if (bias && ((uintptr_t)bias & 15)) return MG_ERR_SHAPE;
-    if (gate && ((uintptr_t)gate & 15)) return MG_ERR_SHAPE;
+    int rc = mg_gemm_check_operands(A, lda, Wt, ldw, bias, gate, M, N, K, BK, 8);
+    if (rc == MG_ERR_ARG || !out || epilogue < 0 || epilogue > 3) return MG_ERR_ARG;
+    if (rc != MG_OK) return rc;
+    if ((ldo & 3) || ((uintptr_t)out & 15)) return MG_ERR_SHAPE;
     if (M == 0) return MG_OK;
 #ifdef MG_AB_BUILD
     const int variant = g_gemm_variant ? g_gemm_variant : 12;
@@ -196,21 +175,10 @@ extern "C" int mg_gemm_bf16(const uint16_t* A, int64_t lda, const uint16_t* Wt, 
         return mg_gemm_v12_launch(A, lda, Wt, ldw, bias, M, N, K, epilogue, out, ldo, gate, (hipStream_t)stream);
     if (variant >= 2 && M > 128)  // tiny M: the 128-row tile wastes less (the 256x256 variants fall through to here for narrow shapes)
         return mg_gemm_v2_launch(A, lda, Wt, ldw, bias, M, N, K, epilogue, out, ldo, gate, (hipStream_t)stream);
-    const int64_t tiles_m64 = (M + BM - 1) / BM;
-    const int tiles_n = (N + BN - 1) / BN;
-    if (tiles_m64 * tiles_n > 0x7fffffffLL) return MG_ERR_SHAPE;
-    const int tiles_m = (int)tiles_m64;
+    int tiles_m, tiles_n;
+    if ((rc = mg_gemm_tile_grid(M, N, BM, BN, &tiles_m, &tiles_n)) != MG_OK) return rc;
     const dim3 grid((unsigned)(tiles_m * tiles_n)), block(GEMM_THREADS);
-    hipStream_t st = (hipStream_t)stream;
-#define LAUNCH(E)                                                                                      \
-    hipLaunchKernelGGL(gemm_bf16_kernel<E>, grid, block, 0, st, A, lda, Wt, ldw, bias, M, N, K, out, ldo, \
-                       gate, tiles_m, tiles_n)
-    switch (epilogue) {
-        case MG_EPI_BIAS_BF16: LAUNCH(MG_EPI_BIAS_BF16); break;
-        case MG_EPI_BIAS_GELU_BF16: LAUNCH(MG_EPI_BIAS_GELU_BF16); break;
-        case MG_EPI_GATE_RESID_F32: LAUNCH(MG_EPI_GATE_RESID_F32); break;
-        default: LAUNCH(MG_EPI_BIAS_F32); break;
-    }
-#undef LAUNCH
+    MG_GEMM_FOR_EPILOGUE(epilogue, hipLaunchKernelGGL(gemm_bf16_kernel<EPI>, grid, block, 0, (hipStream_t)stream, A, lda, Wt, ldw, bias, M,
+                                                      N, K, out, ldo, gate, tiles_m, tiles_n));
     return mg_check_launch();
 }

@@ -14,12 +14,11 @@
 //   * epilogues shaped for the CU's memory pipe, which takes one request per LANE when adjacent lanes are different output rows
 //     (experiments/store_probe.hip): the bf16 outputs store 16 bytes per lane (W rows staged in a permuted order, v11_epilogue_pair),
 //     the fp32 outputs go through LDS and out as whole row segments, the residual read the same way (v11_epilogue_rows).
-// LDS image, XOR swizzle (on the source offset), fragment addressing, MFMA roles and order and tile raster are variant 7's, the
+// LDS image, XOR swizzle (on the source offset), fragment addressing, MFMA roles and order are variant 7's, the tile raster is
+// gemm_raster.h's with variant 8's super-tiles, the
 // epilogue arithmetic is gemm_epilogue.h's element for element: same accumulation order, identical bits
 // (test_gemm_tile_variants_agree, test_gemm_default_epilogues_match_direct_ones).
 #include "gemm_v11_common.h"
-
-extern unsigned long long* g_gemm5_prof;    // gemm_bf16.hip: mg_gemm5_debug_profile
 
 // SCHED = gap stride of the LDS-DMA loads in the generated k-tile (tools/gen_gemm_v11_schedule.py; chosen in the launcher)
 template <int EPI, int SCHED, bool PROF = false>
@@ -36,11 +35,11 @@ __global__ __launch_bounds__(V11_THREADS, 1) void gemm_bf16_v11_kernel(
     constexpr bool PAIRED = EPI == MG_EPI_BIAS_BF16 || EPI == MG_EPI_BIAS_GELU_BF16;
     const int nwg = gridDim.x, bid = blockIdx.x;
     const int total = tiles_m * tiles_n;
-    // XCD-contiguous raster (variant 7): workgroup b of XCD b & 7 takes, in iteration i, position i * (nwg / 8) + (b >> 3) of
-    // its XCD's range [x * q + min(x, r), ...), q = total / 8, r = total % 8
-    const int q8 = total >> 3, r8 = total & 7, xcd = bid & 7;
-    const int xcd_first = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-    const int xcd_count = q8 + (xcd < r8 ? 1 : 0);
+    // XCD-contiguous raster (gemm_raster.h): workgroup b of XCD b & 7 takes, in iteration i, position i * (nwg / 8) + (b >> 3) of
+    // its XCD's range of the tile list
+    const int xcd = bid & 7;
+    int xcd_first, xcd_count;
+    mg_xcd_range(total, xcd, xcd_first, xcd_count);
     const int per_iter = nwg >> 3;        // host guarantees nwg % 8 == 0
     // raster 0: XCD x owns a contiguous range of tile positions (bands of 4 row tiles); rasters 1 / 2 / 3 (nwg == 256): the whole
     // chip works on one super-tile of 16 x 16 / 32 x 8 / 8 x 32 output tiles per iteration (variant 8's rasters)
@@ -60,13 +59,7 @@ __global__ __launch_bounds__(V11_THREADS, 1) void gemm_bf16_v11_kernel(
     const int prow0 = wave * 64;
 
     auto tile_of = [&](int pos, int64_t& m0, int& n0) __attribute__((always_inline)) {
-        const int swz = raster ? pos * 256 + p256 : xcd_first + pos;
-        const int group = swz / per_group;
-        const int first_m = group * GM;
-        const int gsz = (tiles_m - first_m) < GM ? (tiles_m - first_m) : GM;
-        const int in_g = swz - group * per_group;
-        m0 = (int64_t)(first_m + in_g % gsz) * V11_BM;
-        n0 = (in_g / gsz) * V11_BN;
+        mg_tile_of(raster ? pos * 256 + p256 : xcd_first + pos, GM, per_group, tiles_m, V11_BM, V11_BN, m0, n0);
     };
     // Per piece ONE 32-bit byte offset relative to the tile's first row (A + m0 * lda resp. Wt + n0 * ldw live in the buffer
     // resources): row * ld * 2 + (chunk ^ swizzle) * 16, rows past M / N clamped to the last one (never stored).
@@ -97,7 +90,7 @@ __global__ __launch_bounds__(V11_THREADS, 1) void gemm_bf16_v11_kernel(
 
     const int sw = (r16 >> 1) & 7;            // (row >> 1) & 7 of the lane's row in every 16-row block
     const int t3 = G ^ sw;                    // chunk of k-step 0; k-step 1: t3 ^ 4
-    const unsigned lds0 = (unsigned)(uintptr_t)(v11_lptr_t)smem;
+    const unsigned lds0 = (unsigned)(uintptr_t)(mg_lptr_t)smem;
     const int a_row_off = (wm * 128 + r16) * 128;
     const int w_row_off = V11_A_BYTES + (wn * 128 + r16) * 128;
     const int nk = K / V11_BK;
@@ -223,30 +216,19 @@ __global__ __launch_bounds__(V11_THREADS, 1) void gemm_bf16_v11_kernel(
     }
 }
 
-int mg_gemm_v8_launch(const uint16_t* A, int64_t lda, const uint16_t* Wt, int64_t ldw, const float* bias, int64_t M, int N, int K,
-                      int epilogue, void* out, int64_t ldo, const float* gate, hipStream_t st);      // gemm_bf16_v8.hip
-
 static int g_v11_flags = 0;     // measurement bits (mg_gemm_set_variant(110 + flags)): 1 = de-phase the waves, 2 = raster 0 always, 4 = no stores (timing only), 8 = skewed start, 16 = fp32 outputs: direct epilogue, 32 = the every-4th-gap schedule whatever K
 void mg_gemm_v11_set_flags(int f) { g_v11_flags = f; }
 
 int mg_gemm_v11_launch(const uint16_t* A, int64_t lda, const uint16_t* Wt, int64_t ldw, const float* bias, int64_t M,
                        int N, int K, int epilogue, void* out, int64_t ldo, const float* gate, hipStream_t st) {
-    int n_cu = mg_cu_count();
-    if (n_cu < 0) return MG_ERR_LAUNCH;
-    n_cu &= ~7;                                         // one workgroup per CU (128 KiB LDS), a multiple of the 8 XCDs
-    if (n_cu < 8) n_cu = 8;
     // 32-bit byte offsets inside a tile (255 rows x ld x 2 bytes + 128; the fp32 epilogue's 128 rows x ldo x 4) and bf16 pitches that only
     // allow 8-byte stores: variant 8 takes those shapes, as it did when it was the default
     const bool bf16_out = epilogue == MG_EPI_BIAS_BF16 || epilogue == MG_EPI_BIAS_GELU_BF16;
     if (lda * 2 * 256 > 0x7fffffffLL || ldw * 2 * 256 > 0x7fffffffLL || ldo * (bf16_out ? 2 : 4) * 128 > 0x7fffffffLL || (bf16_out && (ldo & 7)))
         return mg_gemm_v8_launch(A, lda, Wt, ldw, bias, M, N, K, epilogue, out, ldo, gate, st);
-    const int64_t tiles_m64 = (M + V11_BM - 1) / V11_BM;
-    const int tiles_n = (N + V11_BN - 1) / V11_BN;
-    if (tiles_m64 * tiles_n > 0x7fffffffLL) return MG_ERR_SHAPE;
-    const int tiles_m = (int)tiles_m64;
-    const int total = tiles_m * tiles_n;
-    int nwg = n_cu;
-    if (total < nwg) nwg = (total + 7) & ~7;          // few tiles: one iteration, still a multiple of 8 (idle ones return)
+    int tiles_m, tiles_n, nwg;      // one workgroup per CU (128 KiB LDS)
+    const int rc = mg_gemm_persistent_grid(M, N, V11_BM, V11_BN, &tiles_m, &tiles_n, &nwg);
+    if (rc != MG_OK) return rc;
     // raster by shape: variant 8's rule (profiles/r03r_gemm_rasters.log)
     const int raster = (nwg == 256 && tiles_n < 32 && !(g_v11_flags & 2)) ? (K > 8192 ? 1 : 3) : 0;
     const dim3 grid((unsigned)nwg), block(V11_THREADS);
@@ -263,21 +245,13 @@ int mg_gemm_v11_launch(const uint16_t* A, int64_t lda, const uint16_t* Wt, int64
                                tiles_m, tiles_n, raster, g_v11_flags, g_gemm5_prof);
         return mg_check_launch();
     }
-#define LAUNCH(E)                                                                                                          \
-    do {                                                                                                                   \
-        if (sched4)                                                                                \
-            hipLaunchKernelGGL((gemm_bf16_v11_kernel<E, 4, false>), grid, block, 0, st, A, lda, Wt, ldw, bias, M, N, K, out, ldo, \
-                               gate, tiles_m, tiles_n, raster, g_v11_flags, nullptr);                                      \
-        else                                                                                                               \
-            hipLaunchKernelGGL((gemm_bf16_v11_kernel<E, 6, false>), grid, block, 0, st, A, lda, Wt, ldw, bias, M, N, K, out, ldo, \
-                               gate, tiles_m, tiles_n, raster, g_v11_flags, nullptr);                                      \
-    } while (0)
-    switch (epilogue) {
-        case MG_EPI_BIAS_BF16: LAUNCH(MG_EPI_BIAS_BF16); break;
-        case MG_EPI_BIAS_GELU_BF16: LAUNCH(MG_EPI_BIAS_GELU_BF16); break;
-        case MG_EPI_GATE_RESID_F32: LAUNCH(MG_EPI_GATE_RESID_F32); break;
-        default: LAUNCH(MG_EPI_BIAS_F32); break;
-    }
-#undef LAUNCH
+    MG_GEMM_FOR_EPILOGUE(
+        epilogue,
+        if (sched4)
+            hipLaunchKernelGGL((gemm_bf16_v11_kernel<EPI, 4, false>), grid, block, 0, st, A, lda, Wt, ldw, bias, M, N, K, out, ldo, gate, tiles_m,
+                               tiles_n, raster, g_v11_flags, nullptr);
+        else
+            hipLaunchKernelGGL((gemm_bf16_v11_kernel<EPI, 6, false>), grid, block, 0, st, A, lda, Wt, ldw, bias, M, N, K, out, ldo, gate, tiles_m,
+                               tiles_n, raster, g_v11_flags, nullptr));
     return mg_check_launch();
 }

@@ -20,10 +20,6 @@
 // closed the last body).  Needs K >= 128 (two k-tiles); the launcher sends anything else to the general 256 x 128 kernel (gemm_bf16_v2.hip).
 #include "gemm_v11_common.h"
 
-#ifdef MG_AB_BUILD
-extern unsigned long long* g_gemm5_prof;    // gemm_bf16.hip: mg_gemm5_debug_profile (A/B library only)
-#endif
-
 // SCHED = which generated body (tools/gen_gemm_v12_schedule.py: SCHEDULES); chosen in the launcher
 // the lane index, re-derived where it is called: two VALU instructions the compiler can neither hoist out of the tile loop nor merge (see set_offsets)
 MG_DEV int v12_lane() {
@@ -47,10 +43,10 @@ __global__ __launch_bounds__(V11_THREADS, 1) void gemm_bf16_v12_kernel(
     constexpr bool PAIRED = EPI == MG_EPI_BIAS_BF16 || EPI == MG_EPI_BIAS_GELU_BF16;
     const int nwg = gridDim.x, bid = blockIdx.x;
     const int total = tiles_m * tiles_n;
-    // rasters: variant 11's (gemm_bf16_v11.hip)
-    const int q8 = total >> 3, r8 = total & 7, xcd = bid & 7;
-    const int xcd_first = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-    const int xcd_count = q8 + (xcd < r8 ? 1 : 0);
+    // rasters: variant 11's (gemm_raster.h)
+    const int xcd = bid & 7;
+    int xcd_first, xcd_count;
+    mg_xcd_range(total, xcd, xcd_first, xcd_count);
     const int per_iter = nwg >> 3;
     const int XR = raster == 2 ? 8 : raster == 3 ? 2 : 4;
     const int SR = 4 * XR;
@@ -72,13 +68,7 @@ __global__ __launch_bounds__(V11_THREADS, 1) void gemm_bf16_v12_kernel(
     const int prow0 = wave * 64;
 
     auto tile_of = [&](int pos, int64_t& m0, int& n0) __attribute__((always_inline)) {
-        const int swz = raster ? pos * 256 + p256 : xcd_first + pos;
-        const int group = swz / per_group;
-        const int first_m = group * GM;
-        const int gsz = (tiles_m - first_m) < GM ? (tiles_m - first_m) : GM;
-        const int in_g = swz - group * per_group;
-        m0 = (int64_t)(first_m + in_g % gsz) * V11_BM;
-        n0 = (in_g / gsz) * V11_BN;
+        mg_tile_of(raster ? pos * 256 + p256 : xcd_first + pos, GM, per_group, tiles_m, V11_BM, V11_BN, m0, n0);
     };
     int voff[NP];
     u32x4_t rs_a, rs_w;
@@ -110,7 +100,7 @@ __global__ __launch_bounds__(V11_THREADS, 1) void gemm_bf16_v12_kernel(
 
     const int sw = (r16 >> 1) & 7;
     const int t3 = G ^ sw;
-    const unsigned lds0 = (unsigned)(uintptr_t)(v11_lptr_t)smem;
+    const unsigned lds0 = (unsigned)(uintptr_t)(mg_lptr_t)smem;
     // per-lane fragment addresses in stage 0: k-step 0 (chunk t3) and k-step 1 (chunk t3 ^ 4)
     const unsigned pa0 = lds0 + (wm * 128 + r16) * 128 + (t3 << 4), pa1 = lds0 + (wm * 128 + r16) * 128 + ((t3 ^ 4) << 4);
     const unsigned pw0 = lds0 + V11_A_BYTES + (wn * 128 + r16) * 128 + (t3 << 4), pw1 = lds0 + V11_A_BYTES + (wn * 128 + r16) * 128 + ((t3 ^ 4) << 4);
@@ -362,9 +352,6 @@ __global__ __launch_bounds__(V11_THREADS, 1) void gemm_bf16_v12_kernel(
     }
 }
 
-int mg_gemm_v2_launch(const uint16_t* A, int64_t lda, const uint16_t* Wt, int64_t ldw, const float* bias, int64_t M, int N, int K,
-                      int epilogue, void* out, int64_t ldo, const float* gate, hipStream_t st);      // gemm_bf16_v2.hip
-
 #ifdef MG_AB_BUILD
 static int g_v12_flags = 0;     // measurement bits (mg_gemm_set_variant(200 + flags)): 1 = fp32 outputs: residual batches not pipelined, 2 = raster 0 always, 4 = no stores (timing only), 8 = touch loads in front of the gated-residual epilogue, 128 = fp32 outputs: no residual loads (timing only), 256 / 512 = fp32 outputs: no nt hint on the stores / the residual loads, 1024 = bf16 outputs: no nt hint on the stores, 2048 / 4096 = the XCD's workgroups start 4 us apart in 32 / 16 phases, 16 = fp32 outputs: direct epilogue, 32 * (1 + s) = generated body s (0 / 2)
 void mg_gemm_v12_set_flags(int f) { g_v12_flags = f; }
@@ -379,17 +366,9 @@ int mg_gemm_v12_launch(const uint16_t* A, int64_t lda, const uint16_t* Wt, int64
         ldo * ((epilogue == MG_EPI_BIAS_BF16 || epilogue == MG_EPI_BIAS_GELU_BF16) ? 2 : 4) * 128 > 0x7fffffffLL ||
         ((epilogue == MG_EPI_BIAS_BF16 || epilogue == MG_EPI_BIAS_GELU_BF16) && (ldo & 7)))
         return mg_gemm_v2_launch(A, lda, Wt, ldw, bias, M, N, K, epilogue, out, ldo, gate, st);
-    int n_cu = mg_cu_count();
-    if (n_cu < 0) return MG_ERR_LAUNCH;
-    n_cu &= ~7;
-    if (n_cu < 8) n_cu = 8;
-    const int64_t tiles_m64 = (M + V11_BM - 1) / V11_BM;
-    const int tiles_n = (N + V11_BN - 1) / V11_BN;
-    if (tiles_m64 * tiles_n > 0x7fffffffLL) return MG_ERR_SHAPE;
-    const int tiles_m = (int)tiles_m64;
-    const int total = tiles_m * tiles_n;
-    int nwg = n_cu;
-    if (total < nwg) nwg = (total + 7) & ~7;
+    int tiles_m, tiles_n, nwg;      // one workgroup per CU (128 KiB LDS)
+    const int rc = mg_gemm_persistent_grid(M, N, V11_BM, V11_BN, &tiles_m, &tiles_n, &nwg);
+    if (rc != MG_OK) return rc;
     const int raster = (nwg == 256 && tiles_n < 32 && !(g_v12_flags & 2)) ? (K > 8192 ? 1 : 3) : 0;      // variant 8's rule
     const dim3 grid((unsigned)nwg), block(V11_THREADS);
     // which generated body: measurement override in bits 5-7 of the flags (mg_gemm_set_variant(200 + 32 * (1 + s))), else body 0 (the six
@@ -404,23 +383,16 @@ int mg_gemm_v12_launch(const uint16_t* A, int64_t lda, const uint16_t* Wt, int64
     hipLaunchKernelGGL((gemm_bf16_v12_kernel<E, S, P>), grid, block, 0, st, A, lda, Wt, ldw, bias, M, N, K, out, ldo, gate, tiles_m, tiles_n, \
                        raster, g_v12_flags & ~0x60, V12_PROF_BUF(P))
 #ifdef MG_AB_BUILD
-#define LAUNCH(E) do { if (sched == 2) LAUNCH_S(E, 2, false); else LAUNCH_S(E, 0, false); } while (0)
     if (g_gemm5_prof && (epilogue == MG_EPI_BIAS_BF16 || epilogue == MG_EPI_GATE_RESID_F32)) {
         if (epilogue == MG_EPI_BIAS_BF16) LAUNCH_S(MG_EPI_BIAS_BF16, 0, true);
         else LAUNCH_S(MG_EPI_GATE_RESID_F32, 0, true);
         return mg_check_launch();
     }
+    MG_GEMM_FOR_EPILOGUE(epilogue, if (sched == 2) LAUNCH_S(EPI, 2, false); else LAUNCH_S(EPI, 0, false));
 #else
     (void)sched;
-#define LAUNCH(E) LAUNCH_S(E, 0, false)
+    MG_GEMM_FOR_EPILOGUE(epilogue, LAUNCH_S(EPI, 0, false));
 #endif
-    switch (epilogue) {
-        case MG_EPI_BIAS_BF16: LAUNCH(MG_EPI_BIAS_BF16); break;
-        case MG_EPI_BIAS_GELU_BF16: LAUNCH(MG_EPI_BIAS_GELU_BF16); break;
-        case MG_EPI_GATE_RESID_F32: LAUNCH(MG_EPI_GATE_RESID_F32); break;
-        default: LAUNCH(MG_EPI_BIAS_F32); break;
-    }
-#undef LAUNCH
 #undef LAUNCH_S
 #undef V12_PROF_BUF
     return mg_check_launch();

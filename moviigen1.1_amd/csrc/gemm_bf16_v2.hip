@@ -9,9 +9,9 @@
 // stay in flight), never a full drain.  __syncthreads() would re-insert vmcnt(0) (hipcc drains
 // LDS-DMA at its fences), hence __builtin_amdgcn_s_barrier().
 // LDS image, swizzle, MFMA roles and epilogues are those of gemm_bf16.hip.
-#include "common.h"
 #include "gemm_epilogue.h"
-#include "../../include/moviigen_hip.h"
+#include "gemm_launch.h"
+#include "gemm_raster.h"
 
 #define V2_BM 256
 #define V2_BN 128
@@ -21,10 +21,6 @@
 #define V2_W_BYTES (V2_BN * V2_BK * 2)  // 16 KiB
 #define V2_STAGE (V2_A_BYTES + V2_W_BYTES)
 #define V2_NSTAGE 3
-
-typedef const __attribute__((address_space(1))) void* v2_gptr_t;
-typedef __attribute__((address_space(3))) void* v2_lptr_t;
-MG_DEV void v2_glds16(const void* g, void* l) { __builtin_amdgcn_global_load_lds((v2_gptr_t)g, (v2_lptr_t)l, 16, 0, 0); }
 
 static unsigned long long* g_gemm_prof = nullptr;
 #ifdef MG_AB_BUILD
@@ -47,10 +43,12 @@ __global__ __launch_bounds__(V2_THREADS, 2) void gemm_bf16_v2_kernel(
     };
     __shared__ __attribute__((aligned(16))) char smem[V2_NSTAGE * V2_STAGE];
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    const int GM = 4;  // 4 x 256 = the same 1024-token band as variant 1
+    // workgroup -> tile (XCD split of the grid: gemm_raster.h), bands of 4 x 256 = the same 1024 tokens as variant 1
+    const int bid = blockIdx.x;
+    int xcd_first, xcd_count;
+    mg_xcd_range(gridDim.x, bid & 7, xcd_first, xcd_count);
+    const int swz = xcd_first + (bid >> 3);
+    const int GM = 4;
     const int per_group = GM * tiles_n;
     const int group = swz / per_group;
     const int first_m = group * GM;
@@ -89,9 +87,9 @@ __global__ __launch_bounds__(V2_THREADS, 2) void gemm_bf16_v2_kernel(
         char* lw = smem + (kt % V2_NSTAGE) * V2_STAGE + V2_A_BYTES + wave * 16 * 128;
         const int koff = kt * V2_BK;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v2_glds16(ga[i] + koff, la + i * 8 * 128);
+        for (int i = 0; i < 4; ++i) mg_glds16(ga[i] + koff, la + i * 8 * 128);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) v2_glds16(gw[i] + koff, lw + i * 8 * 128);
+        for (int i = 0; i < 2; ++i) mg_glds16(gw[i] + koff, lw + i * 8 * 128);
     };
 
     const int sw = (l31 >> 1) & 7;
@@ -157,8 +155,8 @@ __global__ __launch_bounds__(V2_THREADS, 2) void gemm_bf16_v2_kernel(
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[kk & 1][i], fa[kk & 1][j], acc[i][j], 0, 0, 0);
                 const int piece = kk * 2 + i;      // one DMA piece behind every second MFMA (6 pieces, steps 0..2)
                 if (piece < 6 && refill) {
-                    if (piece < 4) v2_glds16(ga[piece] + koff2, la + piece * 8 * 128);
-                    else v2_glds16(gw[piece - 4] + koff2, lw + (piece - 4) * 8 * 128);
+                    if (piece < 4) mg_glds16(ga[piece] + koff2, la + piece * 8 * 128);
+                    else mg_glds16(gw[piece - 4] + koff2, lw + (piece - 4) * 8 * 128);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -177,25 +175,16 @@ __global__ __launch_bounds__(V2_THREADS, 2) void gemm_bf16_v2_kernel(
 
 int mg_gemm_v2_launch(const uint16_t* A, int64_t lda, const uint16_t* Wt, int64_t ldw, const float* bias, int64_t M,
                       int N, int K, int epilogue, void* out, int64_t ldo, const float* gate, hipStream_t st) {
-    const int64_t tiles_m64 = (M + V2_BM - 1) / V2_BM;
-    const int tiles_n = (N + V2_BN - 1) / V2_BN;
-    if (tiles_m64 * tiles_n > 0x7fffffffLL) return MG_ERR_SHAPE;
-    const int tiles_m = (int)tiles_m64;
+    int tiles_m, tiles_n;
+    const int rc = mg_gemm_tile_grid(M, N, V2_BM, V2_BN, &tiles_m, &tiles_n);
+    if (rc != MG_OK) return rc;
     const dim3 grid((unsigned)(tiles_m * tiles_n)), block(V2_THREADS);
-#define LAUNCH(E)                                                                                          \
-    hipLaunchKernelGGL(gemm_bf16_v2_kernel<E>, grid, block, 0, st, A, lda, Wt, ldw, bias, M, N, K, out, ldo, \
-                       gate, tiles_m, tiles_n, nullptr)
     if (g_gemm_prof && epilogue == MG_EPI_BIAS_BF16) {
         hipLaunchKernelGGL((gemm_bf16_v2_kernel<MG_EPI_BIAS_BF16, true>), grid, block, 0, st, A, lda, Wt, ldw, bias, M, N, K,
                            out, ldo, gate, tiles_m, tiles_n, g_gemm_prof);
         return mg_check_launch();
     }
-    switch (epilogue) {
-        case MG_EPI_BIAS_BF16: LAUNCH(MG_EPI_BIAS_BF16); break;
-        case MG_EPI_BIAS_GELU_BF16: LAUNCH(MG_EPI_BIAS_GELU_BF16); break;
-        case MG_EPI_GATE_RESID_F32: LAUNCH(MG_EPI_GATE_RESID_F32); break;
-        default: LAUNCH(MG_EPI_BIAS_F32); break;
-    }
-#undef LAUNCH
+    MG_GEMM_FOR_EPILOGUE(epilogue, hipLaunchKernelGGL(gemm_bf16_v2_kernel<EPI>, grid, block, 0, st, A, lda, Wt, ldw, bias, M, N, K, out, ldo,
+                                                      gate, tiles_m, tiles_n, nullptr));
     return mg_check_launch();
 }

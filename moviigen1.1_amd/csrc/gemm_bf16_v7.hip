@@ -20,13 +20,13 @@
 // fetches the FIRST k-tile of the workgroup's next tile.  The operands of tile T+1 are therefore in flight while the
 // epilogue of tile T runs (variant 5 starts every tile cold: dispatch, 16 pointer set-ups, a full DMA round trip
 // with the matrix pipe idle), and one launch of <= 256 workgroups replaces 10-30 thousand workgroup dispatches.
-// Tile order = variant 5's XCD-contiguous raster evaluated on the virtual workgroup id (iteration * grid + block):
+// Tile order = variant 5's XCD-contiguous raster (now gemm_raster.h) evaluated on the virtual workgroup id (iteration * grid + block):
 // in iteration i the 32 workgroups of an XCD work on 32 consecutive tiles of that XCD's range (4 token bands x 8
 // feature panels), streaming through K together, so an A or W k-slice is fetched from the fabric once per XCD.
 // Same arithmetic and accumulation order (k ascending, fp32) as variants 1/2/5/6: identical bits.
-#include "common.h"
 #include "gemm_epilogue.h"
-#include "../../include/moviigen_hip.h"
+#include "gemm_launch.h"
+#include "gemm_raster.h"
 
 #define V7_BM 256
 #define V7_BN 256
@@ -35,10 +35,6 @@
 #define V7_A_BYTES (V7_BM * V7_BK * 2)  // 32 KiB
 #define V7_W_BYTES (V7_BN * V7_BK * 2)  // 32 KiB
 #define V7_STAGE (V7_A_BYTES + V7_W_BYTES)
-
-typedef const __attribute__((address_space(1))) void* v7_gptr_t;
-typedef __attribute__((address_space(3))) void* v7_lptr_t;
-MG_DEV void v7_glds16(const void* g, void* l) { __builtin_amdgcn_global_load_lds((v7_gptr_t)g, (v7_lptr_t)l, 16, 0, 0); }
 
 template <int OFF>
 MG_DEV void v7_rd(bf16x8_t& dst, unsigned addr) {
@@ -71,8 +67,6 @@ MG_DEV void v7_rd_slot(int slot, bf16x8_t (&fa)[8], bf16x8_t (&fw)[8], unsigned 
     }
 }
 
-extern unsigned long long* g_gemm5_prof;    // gemm_bf16.hip: mg_gemm5_debug_profile
-
 // The wave's 16 LDS-DMA pieces of the next k-tile ride behind the 16 MFMA groups of k-step 0.  s_memtime per k-tile
 // (M = 131 040, N = K = 5120, profiles/r03e_gemm_dma_schedules.txt): barrier wait 119 + 1774 (k-step 0) + 1036 (k-step 1
 // = the MFMA floor) cycles.  Moving pieces into k-step 1 shortens k-step 0 by ~35 cycles per piece but they then land
@@ -89,11 +83,10 @@ __global__ __launch_bounds__(V7_THREADS, 1) void gemm_bf16_v7_kernel(
 
     const int nwg = gridDim.x, bid = blockIdx.x;
     const int total = tiles_m * tiles_n;
-    // XCD-contiguous raster of variant 5 on the virtual id v: workgroup b of XCD b & 7 takes, in iteration i, position
-    // i * (nwg / 8) + (b >> 3) of its XCD's range [x * q + min(x, r), ...), q = total / 8, r = total % 8
-    const int q8 = total >> 3, r8 = total & 7, xcd = bid & 7;
-    const int xcd_first = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-    const int xcd_count = q8 + (xcd < r8 ? 1 : 0);
+    // XCD-contiguous raster of variant 5 on the virtual id v (gemm_raster.h): workgroup b of XCD b & 7 takes, in iteration i,
+    // position i * (nwg / 8) + (b >> 3) of its XCD's range of the tile list
+    int xcd_first, xcd_count;
+    mg_xcd_range(total, bid & 7, xcd_first, xcd_count);
     const int per_iter = nwg >> 3;        // host guarantees nwg % 8 == 0
     const int GM = 4;                     // 4 x 256 = a 1024-token band
     const int per_group = GM * tiles_n;
@@ -109,13 +102,7 @@ __global__ __launch_bounds__(V7_THREADS, 1) void gemm_bf16_v7_kernel(
     (void)colsw;
 
     auto tile_of = [&](int pos, int64_t& m0, int& n0) __attribute__((always_inline)) {
-        const int swz = xcd_first + pos;
-        const int group = swz / per_group;
-        const int first_m = group * GM;
-        const int gsz = (tiles_m - first_m) < GM ? (tiles_m - first_m) : GM;
-        const int in_g = swz - group * per_group;
-        m0 = (int64_t)(first_m + in_g % gsz) * V7_BM;
-        n0 = (in_g / gsz) * V7_BN;
+        mg_tile_of(xcd_first + pos, GM, per_group, tiles_m, V7_BM, V7_BN, m0, n0);
     };
     const uint16_t* gp[NP];
     auto set_pointers = [&](int64_t m0, int n0) __attribute__((always_inline)) {
@@ -139,7 +126,7 @@ __global__ __launch_bounds__(V7_THREADS, 1) void gemm_bf16_v7_kernel(
 
     const int sw = (r16 >> 1) & 7;            // (row >> 1) & 7 of the lane's row in every 16-row block
     const int t3 = G ^ sw;                    // chunk of k-step 0; k-step 1: t3 ^ 4
-    const unsigned lds0 = (unsigned)(uintptr_t)(v7_lptr_t)smem;
+    const unsigned lds0 = (unsigned)(uintptr_t)(mg_lptr_t)smem;
     const int a_row_off = (wm * 128 + r16) * 128;
     const int w_row_off = V7_A_BYTES + (wn * 128 + r16) * 128;
     const int nk = K / V7_BK;
@@ -152,7 +139,7 @@ __global__ __launch_bounds__(V7_THREADS, 1) void gemm_bf16_v7_kernel(
     set_pointers(m0, n0);
     {   // cold start of the FIRST tile only
 #pragma unroll
-        for (int i = 0; i < NP; ++i) v7_glds16(gp[i], smem + piece_lds(i));
+        for (int i = 0; i < NP; ++i) mg_glds16(gp[i], smem + piece_lds(i));
     }
     int gk = 0;                                   // k-tiles consumed so far by this workgroup: stage = gk & 1
     for (;;) {
@@ -227,7 +214,7 @@ __global__ __launch_bounds__(V7_THREADS, 1) void gemm_bf16_v7_kernel(
                     __builtin_amdgcn_sched_barrier(0);
                     if (ks == 0) {
                         v7_rd_slot(grp, fa[1], fw[1], abase, wbase);                       // one read of k-step 1 ...
-                        v7_glds16(gp[grp] + koff2, lnext + piece_lds(grp));                // ... and one LDS-DMA piece of the next k-tile
+                        mg_glds16(gp[grp] + koff2, lnext + piece_lds(grp));                // ... and one LDS-DMA piece of the next k-tile
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -253,32 +240,16 @@ __global__ __launch_bounds__(V7_THREADS, 1) void gemm_bf16_v7_kernel(
 
 int mg_gemm_v7_launch(const uint16_t* A, int64_t lda, const uint16_t* Wt, int64_t ldw, const float* bias, int64_t M,
                       int N, int K, int epilogue, void* out, int64_t ldo, const float* gate, hipStream_t st) {
-    int n_cu = mg_cu_count();
-    if (n_cu < 0) return MG_ERR_LAUNCH;
-    n_cu &= ~7;                                         // one workgroup per CU (128 KiB LDS), a multiple of the 8 XCDs
-    if (n_cu < 8) n_cu = 8;
-    const int64_t tiles_m64 = (M + V7_BM - 1) / V7_BM;
-    const int tiles_n = (N + V7_BN - 1) / V7_BN;
-    if (tiles_m64 * tiles_n > 0x7fffffffLL) return MG_ERR_SHAPE;
-    const int tiles_m = (int)tiles_m64;
-    const int total = tiles_m * tiles_n;
-    int nwg = n_cu;
-    if (total < nwg) nwg = (total + 7) & ~7;          // few tiles: one iteration, still a multiple of 8 (idle ones return)
+    int tiles_m, tiles_n, nwg;      // one workgroup per CU (128 KiB LDS)
+    const int rc = mg_gemm_persistent_grid(M, N, V7_BM, V7_BN, &tiles_m, &tiles_n, &nwg);
+    if (rc != MG_OK) return rc;
     const dim3 grid((unsigned)nwg), block(V7_THREADS);
     if (g_gemm5_prof && epilogue == MG_EPI_BIAS_BF16) {
         hipLaunchKernelGGL((gemm_bf16_v7_kernel<MG_EPI_BIAS_BF16, true>), grid, block, 0, st, A, lda, Wt, ldw, bias, M, N, K,
                            out, ldo, gate, tiles_m, tiles_n, g_gemm5_prof);
         return mg_check_launch();
     }
-#define LAUNCH(E)                                                                                          \
-    hipLaunchKernelGGL((gemm_bf16_v7_kernel<E, false>), grid, block, 0, st, A, lda, Wt, ldw, bias, M, N, K, out, ldo, \
-                       gate, tiles_m, tiles_n, nullptr)
-    switch (epilogue) {
-        case MG_EPI_BIAS_BF16: LAUNCH(MG_EPI_BIAS_BF16); break;
-        case MG_EPI_BIAS_GELU_BF16: LAUNCH(MG_EPI_BIAS_GELU_BF16); break;
-        case MG_EPI_GATE_RESID_F32: LAUNCH(MG_EPI_GATE_RESID_F32); break;
-        default: LAUNCH(MG_EPI_BIAS_F32); break;
-    }
-#undef LAUNCH
+    MG_GEMM_FOR_EPILOGUE(epilogue, hipLaunchKernelGGL((gemm_bf16_v7_kernel<EPI, false>), grid, block, 0, st, A, lda, Wt, ldw, bias, M, N, K, out,
+                                                      ldo, gate, tiles_m, tiles_n, nullptr));
     return mg_check_launch();
 }

@@ -19,9 +19,9 @@
 // k-tile t, whose reads retired before the barrier in between — for either group.
 // Same LDS image, swizzle, persistent XCD-contiguous tile loop, next-tile prefetch and epilogue as variant 7; same
 // arithmetic and accumulation order: identical bits.
-#include "common.h"
 #include "gemm_epilogue.h"
-#include "../../include/moviigen_hip.h"
+#include "gemm_launch.h"
+#include "gemm_raster.h"
 
 #define V8_BM 256
 #define V8_BN 256
@@ -30,10 +30,6 @@
 #define V8_A_BYTES (V8_BM * V8_BK * 2)  // 32 KiB
 #define V8_W_BYTES (V8_BN * V8_BK * 2)  // 32 KiB
 #define V8_STAGE (V8_A_BYTES + V8_W_BYTES)
-
-typedef const __attribute__((address_space(1))) void* v8_gptr_t;
-typedef __attribute__((address_space(3))) void* v8_lptr_t;
-MG_DEV void v8_glds16(const void* g, void* l) { __builtin_amdgcn_global_load_lds((v8_gptr_t)g, (v8_lptr_t)l, 16, 0, 0); }
 
 template <int OFF>
 MG_DEV void v8_rd(bf16x8_t& dst, unsigned addr) {
@@ -48,8 +44,6 @@ MG_DEV void v8_rd4(bf16x8_t (&f)[4], unsigned base) {
     v8_rd<(B0 + 3) * 2048>(f[3], base);
 }
 
-extern unsigned long long* g_gemm5_prof;    // gemm_bf16.hip: mg_gemm5_debug_profile
-
 // Wave priorities (s_setprio around the MFMA part, around the load part, static for the second-dispatched group) were
 // measured and make no difference here (profiles/r03i_gemm_v8_prio.log: all within 0.5 %): none is used.
 template <int EPI, bool PROF = false>
@@ -62,9 +56,9 @@ __global__ __launch_bounds__(V8_THREADS, 2) void gemm_bf16_v8_kernel(
 
     const int nwg = gridDim.x, bid = blockIdx.x;
     const int total = tiles_m * tiles_n;
-    const int q8 = total >> 3, r8 = total & 7, xcd = bid & 7;
-    const int xcd_first = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-    const int xcd_count = q8 + (xcd < r8 ? 1 : 0);
+    const int xcd = bid & 7;
+    int xcd_first, xcd_count;
+    mg_xcd_range(total, xcd, xcd_first, xcd_count);      // gemm_raster.h, as are mg_tile_of and mg_supertile_pos below
     const int per_iter = nwg >> 3;        // host guarantees nwg % 8 == 0
     // raster 0: XCD x owns a contiguous range of tile positions (bands of 4 row tiles, its 32 workgroups = 4 x 8 tiles).
     // rasters 1 / 2 / 3 (nwg == 256): the WHOLE chip works on one super-tile of 16 x 16 / 32 x 8 / 8 x 32 output tiles per
@@ -87,13 +81,7 @@ __global__ __launch_bounds__(V8_THREADS, 2) void gemm_bf16_v8_kernel(
     const int prow0 = wave * 32;
 
     auto tile_of = [&](int pos, int64_t& m0, int& n0) __attribute__((always_inline)) {
-        const int swz = raster ? pos * 256 + p256 : xcd_first + pos;
-        const int group = swz / per_group;
-        const int first_m = group * GM;
-        const int gsz = (tiles_m - first_m) < GM ? (tiles_m - first_m) : GM;
-        const int in_g = swz - group * per_group;
-        m0 = (int64_t)(first_m + in_g % gsz) * V8_BM;
-        n0 = (in_g / gsz) * V8_BN;
+        mg_tile_of(raster ? pos * 256 + p256 : xcd_first + pos, GM, per_group, tiles_m, V8_BM, V8_BN, m0, n0);
     };
     const uint16_t* gp[NP];
     auto set_pointers = [&](int64_t m0, int n0) __attribute__((always_inline)) {
@@ -117,7 +105,7 @@ __global__ __launch_bounds__(V8_THREADS, 2) void gemm_bf16_v8_kernel(
 
     const int sw = (r16 >> 1) & 7;            // (row >> 1) & 7 of the lane's row in every 16-row block
     const int t3 = G ^ sw;                    // chunk of k-step 0; k-step 1: t3 ^ 4
-    const unsigned lds0 = (unsigned)(uintptr_t)(v8_lptr_t)smem;
+    const unsigned lds0 = (unsigned)(uintptr_t)(mg_lptr_t)smem;
     const int a_row_off = (wm * 128 + r16) * 128;
     const int w_row_off = V8_A_BYTES + (wn * 64 + r16) * 128;
     const int nk = K / V8_BK;
@@ -129,7 +117,7 @@ __global__ __launch_bounds__(V8_THREADS, 2) void gemm_bf16_v8_kernel(
     tile_of(pos, m0, n0);
     set_pointers(m0, n0);
 #pragma unroll
-    for (int i = 0; i < NP; ++i) v8_glds16(gp[i], smem + piece_lds(i));      // cold start of the FIRST tile only
+    for (int i = 0; i < NP; ++i) mg_glds16(gp[i], smem + piece_lds(i));      // cold start of the FIRST tile only
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     if (wm == 1) __builtin_amdgcn_s_barrier();          // group Y runs one barrier behind group X from here on
@@ -169,7 +157,7 @@ __global__ __launch_bounds__(V8_THREADS, 2) void gemm_bf16_v8_kernel(
                 else v8_rd4<0>(fa, ab1);
                 if (ph < 2) {
 #pragma unroll
-                    for (int p = 4 * ph; p < 4 * ph + 4; ++p) v8_glds16(gp[p] + koff2, lnext + piece_lds(p));
+                    for (int p = 4 * ph; p < 4 * ph + 4; ++p) mg_glds16(gp[p] + koff2, lnext + piece_lds(p));
                 }
                 if (ph == 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // my pieces of the next k-tile have landed
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // my fragment reads are retired
@@ -208,17 +196,9 @@ __global__ __launch_bounds__(V8_THREADS, 2) void gemm_bf16_v8_kernel(
 
 int mg_gemm_v8_launch(const uint16_t* A, int64_t lda, const uint16_t* Wt, int64_t ldw, const float* bias, int64_t M,
                       int N, int K, int epilogue, void* out, int64_t ldo, const float* gate, hipStream_t st) {
-    int n_cu = mg_cu_count();
-    if (n_cu < 0) return MG_ERR_LAUNCH;
-    n_cu &= ~7;                                         // one workgroup per CU (128 KiB LDS), a multiple of the 8 XCDs
-    if (n_cu < 8) n_cu = 8;
-    const int64_t tiles_m64 = (M + V8_BM - 1) / V8_BM;
-    const int tiles_n = (N + V8_BN - 1) / V8_BN;
-    if (tiles_m64 * tiles_n > 0x7fffffffLL) return MG_ERR_SHAPE;
-    const int tiles_m = (int)tiles_m64;
-    const int total = tiles_m * tiles_n;
-    int nwg = n_cu;
-    if (total < nwg) nwg = (total + 7) & ~7;          // few tiles: one iteration, still a multiple of 8 (idle ones return)
+    int tiles_m, tiles_n, nwg;      // one workgroup per CU (128 KiB LDS)
+    const int rc = mg_gemm_persistent_grid(M, N, V8_BM, V8_BN, &tiles_m, &tiles_n, &nwg);
+    if (rc != MG_OK) return rc;
     // Raster by shape (profiles/r03o_gemm_raster.log, r03r_gemm_rasters.log; M = 131040, TFLOP/s for rasters 0 / 1 / 2 / 3):
     //   q|k|v 1295 / 1267 / 1299 / 1231, ffn.0 1214 / 1186 / 1219 / 1184            -> wide outputs stay on raster 0
     //   o (K 5120, gated residual) 1076 / 1129 / 1063 / 1153, cross-q 1236 / 1286 / 1261 / 1284   -> raster 3 (8 x 32)
@@ -230,15 +210,7 @@ int mg_gemm_v8_launch(const uint16_t* A, int64_t lda, const uint16_t* Wt, int64_
                            out, ldo, gate, tiles_m, tiles_n, raster, g_gemm5_prof);
         return mg_check_launch();
     }
-#define LAUNCH(E)                                                                                          \
-    hipLaunchKernelGGL((gemm_bf16_v8_kernel<E, false>), grid, block, 0, st, A, lda, Wt, ldw, bias, M, N, K, out, ldo, \
-                       gate, tiles_m, tiles_n, raster, nullptr)
-    switch (epilogue) {
-        case MG_EPI_BIAS_BF16: LAUNCH(MG_EPI_BIAS_BF16); break;
-        case MG_EPI_BIAS_GELU_BF16: LAUNCH(MG_EPI_BIAS_GELU_BF16); break;
-        case MG_EPI_GATE_RESID_F32: LAUNCH(MG_EPI_GATE_RESID_F32); break;
-        default: LAUNCH(MG_EPI_BIAS_F32); break;
-    }
-#undef LAUNCH
+    MG_GEMM_FOR_EPILOGUE(epilogue, hipLaunchKernelGGL((gemm_bf16_v8_kernel<EPI, false>), grid, block, 0, st, A, lda, Wt, ldw, bias, M, N, K, out,
+                                                      ldo, gate, tiles_m, tiles_n, raster, nullptr));
     return mg_check_launch();
 }

@@ -22,10 +22,10 @@
 // byte G down.  Weights are the MFMA's A operand (feature rows), activations its B operand (token columns), as in every
 // bf16 variant: lane (tok, G) owns token tok of block j and features 16 i + 4 G .. + 3.
 // Accumulation: k-tiles ascending, fp32, one workgroup per output tile, no atomics: the result does not depend on the launch.
-#include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_launch.h"
+#include "gemm_raster.h"
 #include "mxfp8_quant.h"
-#include "../../include/moviigen_hip.h"
 
 #define MX_BM 256
 #define MX_BN 256
@@ -39,10 +39,6 @@
 
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;
 typedef __attribute__((ext_vector_type(4))) int i32x4_t;
-typedef const __attribute__((address_space(1))) void* mx_gptr_t;
-typedef __attribute__((address_space(3))) void* mx_lptr_t;
-MG_DEV void mx_glds16(const void* g, void* l) { __builtin_amdgcn_global_load_lds((mx_gptr_t)g, (mx_lptr_t)l, 16, 0, 0); }
-MG_DEV void mx_glds4(const void* g, void* l) { __builtin_amdgcn_global_load_lds((mx_gptr_t)g, (mx_lptr_t)l, 4, 0, 0); }
 
 // LDS reads of the k-loop are inline asm with hand-counted lgkmcnt waits, as in gemm_bf16_v7.hip: hipcc puts a vmcnt(0) in front
 // of every C++ LDS read that follows an LDS-DMA in program order (it must assume they alias), and with more than 15 reads in
@@ -173,11 +169,10 @@ __global__ __launch_bounds__(MX_THREADS, 1) void gemm_mxfp8_kernel(
 
     const int nwg = gridDim.x, bid = blockIdx.x;
     const int total = tiles_m * tiles_n;
-    // variant 7's raster: workgroup b of XCD b & 7 takes, in iteration i, position i * (nwg / 8) + (b >> 3) of its XCD's
+    // variant 7's raster (gemm_raster.h): workgroup b of XCD b & 7 takes, in iteration i, position i * (nwg / 8) + (b >> 3) of its XCD's
     // contiguous range of the tile list; 4 x 256-token bands x all feature panels per group
-    const int q8 = total >> 3, r8 = total & 7, xcd = bid & 7;
-    const int xcd_first = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-    const int xcd_count = q8 + (xcd < r8 ? 1 : 0);
+    int xcd_first, xcd_count;
+    mg_xcd_range(total, bid & 7, xcd_first, xcd_count);
     const int per_iter = nwg >> 3;        // host guarantees nwg % 8 == 0
     const int GM = 4;
     const int per_group = GM * tiles_n;
@@ -191,13 +186,7 @@ __global__ __launch_bounds__(MX_THREADS, 1) void gemm_mxfp8_kernel(
     const int prow0 = wave * 64;
 
     auto tile_of = [&](int pos, int64_t& m0, int& n0) __attribute__((always_inline)) {
-        const int swz = xcd_first + pos;
-        const int group = swz / per_group;
-        const int first_m = group * GM;
-        const int gsz = (tiles_m - first_m) < GM ? (tiles_m - first_m) : GM;
-        const int in_g = swz - group * per_group;
-        m0 = (int64_t)(first_m + in_g % gsz) * MX_BM;
-        n0 = (in_g / gsz) * MX_BN;
+        mg_tile_of(xcd_first + pos, GM, per_group, tiles_m, MX_BM, MX_BN, m0, n0);
     };
     const uint8_t* gp[NP];
     const uint8_t *gsa, *gsw;                    // this thread's scale dwords: tile row tid of A and of W
@@ -233,7 +222,7 @@ __global__ __launch_bounds__(MX_THREADS, 1) void gemm_mxfp8_kernel(
     const int w_off0 = MX_A_BYTES + (wn * 128 + r16) * 128 + (t3 << 4), w_off1 = MX_A_BYTES + (wn * 128 + r16) * 128 + ((t3 ^ 4) << 4);
     const int sa_off = MX_SA_OFF + (wm * 128 + r16) * 4, sw_off = MX_SW_OFF + (wn * 128 + r16) * 4;
     const int sshift = G * 8;
-    const unsigned lds0 = (unsigned)(uintptr_t)(mx_lptr_t)smem;
+    const unsigned lds0 = (unsigned)(uintptr_t)(mg_lptr_t)smem;
     const int nk = K / MX_BK;
 
     int pos = bid >> 3;
@@ -244,9 +233,9 @@ __global__ __launch_bounds__(MX_THREADS, 1) void gemm_mxfp8_kernel(
     set_pointers(m0, n0);
     {   // cold start of the FIRST tile only
 #pragma unroll
-        for (int i = 0; i < NP; ++i) mx_glds16(gp[i], smem + piece_lds(i));
-        mx_glds4(gsa, smem + MX_SA_OFF + wave * 256);
-        mx_glds4(gsw, smem + MX_SW_OFF + wave * 256);
+        for (int i = 0; i < NP; ++i) mg_glds16(gp[i], smem + piece_lds(i));
+        mg_glds4(gsa, smem + MX_SA_OFF + wave * 256);
+        mg_glds4(gsw, smem + MX_SW_OFF + wave * 256);
     }
     int gk = 0;                                   // k-tiles consumed so far by this workgroup: stage = gk & 1
     for (;;) {
@@ -332,9 +321,9 @@ __global__ __launch_bounds__(MX_THREADS, 1) void gemm_mxfp8_kernel(
                     slot(8 + 2 * grp);
                     slot(9 + 2 * grp);
                 }
-                mx_glds16(gp[grp] + koff2, lnext + piece_lds(grp));     // one LDS-DMA piece of the next k-tile per group
-                if (grp == 14) mx_glds4(gsa + soff2, lnext + MX_SA_OFF + wave * 256);
-                if (grp == 15) mx_glds4(gsw + soff2, lnext + MX_SW_OFF + wave * 256);
+                mg_glds16(gp[grp] + koff2, lnext + piece_lds(grp));     // one LDS-DMA piece of the next k-tile per group
+                if (grp == 14) mg_glds4(gsa + soff2, lnext + MX_SA_OFF + wave * 256);
+                if (grp == 15) mg_glds4(gsw + soff2, lnext + MX_SW_OFF + wave * 256);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -350,30 +339,14 @@ __global__ __launch_bounds__(MX_THREADS, 1) void gemm_mxfp8_kernel(
     }
 }
 
-// what both entry points ask of the operands
+// what both entry points ask of the operands: the checks every GEMM shares (gemm_launch.h), then the scale arrays, N and pitch >= extent
 static int mx_gemm_check(const uint8_t* Aq, int64_t lda, const uint8_t* As, int64_t ldas, const uint8_t* Wq, int64_t ldw,
-                         const uint8_t* Ws, int64_t ldws, const float* bias, int64_t M, int N, int K) {
-    if (!Aq || !As || !Wq || !Ws) return MG_ERR_ARG;
-    if (M < 0 || N <= 0 || K <= 0 || (K % MX_BK) || (N % 16)) return MG_ERR_SHAPE;
-    if (lda < K || ldw < K || ldas < K / 32 || ldws < K / 32) return MG_ERR_SHAPE;
-    if ((lda & 15) || (ldw & 15) || (ldas & 3) || (ldws & 3)) return MG_ERR_SHAPE;
-    if (((uintptr_t)Aq & 15) || ((uintptr_t)Wq & 15) || ((uintptr_t)As & 3) || ((uintptr_t)Ws & 3)) return MG_ERR_SHAPE;
-    if (bias && ((uintptr_t)bias & 15)) return MG_ERR_SHAPE;
-    return MG_OK;
-}
-// and the launch geometry (M > 0)
-static int mx_gemm_grid(int64_t M, int N, int* tiles_m, int* tiles_n, int* nwg) {
-    int n_cu = mg_cu_count();
-    if (n_cu < 0) return MG_ERR_LAUNCH;
-    n_cu &= ~7;                                         // one workgroup per CU (132 KiB LDS), a multiple of the 8 XCDs
-    if (n_cu < 8) n_cu = 8;
-    const int64_t tiles_m64 = (M + MX_BM - 1) / MX_BM;
-    *tiles_n = (N + MX_BN - 1) / MX_BN;
-    if (tiles_m64 * *tiles_n > 0x7fffffffLL) return MG_ERR_SHAPE;
-    *tiles_m = (int)tiles_m64;
-    const int total = *tiles_m * *tiles_n;
-    *nwg = n_cu;
-    if (total < *nwg) *nwg = (total + 7) & ~7;          // few tiles: one iteration, still a multiple of 8 (idle ones return)
+                         const uint8_t* Ws, int64_t ldws, const float* bias, const float* gate, int64_t M, int N, int K) {
+    if (!As || !Ws) return MG_ERR_ARG;
+    const int rc = mg_gemm_check_operands(Aq, lda, Wq, ldw, bias, gate, M, N, K, MX_BK, 16);
+    if (rc != MG_OK) return rc;
+    if ((N % 16) || lda < K || ldw < K || ldas < K / 32 || ldws < K / 32) return MG_ERR_SHAPE;
+    if ((ldas & 3) || (ldws & 3) || ((uintptr_t)As & 3) || ((uintptr_t)Ws & 3)) return MG_ERR_SHAPE;
     return MG_OK;
 }
 
@@ -381,26 +354,16 @@ extern "C" int mg_gemm_mxfp8(const uint8_t* Aq, int64_t lda, const uint8_t* As, 
                              const uint8_t* Ws, int64_t ldws, const float* bias, int64_t M, int N, int K, int epilogue,
                              void* out, int64_t ldo, const float* gate, void* stream) {
     if (!out) return MG_ERR_ARG;
-    int rc = mx_gemm_check(Aq, lda, As, ldas, Wq, ldw, Ws, ldws, bias, M, N, K);
+    int rc = mx_gemm_check(Aq, lda, As, ldas, Wq, ldw, Ws, ldws, bias, gate, M, N, K);
     if (rc == MG_ERR_ARG || epilogue < 0 || epilogue > 3) return MG_ERR_ARG;
     if (rc != MG_OK) return rc;
     if (ldo < N || (ldo & 3) || ((uintptr_t)out & 15)) return MG_ERR_SHAPE;
-    if (gate && ((uintptr_t)gate & 15)) return MG_ERR_SHAPE;
     if (M == 0) return MG_OK;
-    int tiles_m, tiles_n, nwg;
-    if ((rc = mx_gemm_grid(M, N, &tiles_m, &tiles_n, &nwg)) != MG_OK) return rc;
+    int tiles_m, tiles_n, nwg;      // one workgroup per CU (132 KiB LDS)
+    if ((rc = mg_gemm_persistent_grid(M, N, MX_BM, MX_BN, &tiles_m, &tiles_n, &nwg)) != MG_OK) return rc;
     const dim3 grid((unsigned)nwg), block(MX_THREADS);
-    hipStream_t st = (hipStream_t)stream;
-#define LAUNCH(E)                                                                                                    \
-    hipLaunchKernelGGL((gemm_mxfp8_kernel<E>), grid, block, 0, st, Aq, lda, As, ldas, Wq, ldw, Ws, ldws, bias, M, N, K, \
-                       out, ldo, gate, tiles_m, tiles_n, MxQOut<false>{})
-    switch (epilogue) {
-        case MG_EPI_BIAS_BF16: LAUNCH(MG_EPI_BIAS_BF16); break;
-        case MG_EPI_BIAS_GELU_BF16: LAUNCH(MG_EPI_BIAS_GELU_BF16); break;
-        case MG_EPI_GATE_RESID_F32: LAUNCH(MG_EPI_GATE_RESID_F32); break;
-        default: LAUNCH(MG_EPI_BIAS_F32); break;
-    }
-#undef LAUNCH
+    MG_GEMM_FOR_EPILOGUE(epilogue, hipLaunchKernelGGL((gemm_mxfp8_kernel<EPI>), grid, block, 0, (hipStream_t)stream, Aq, lda, As, ldas, Wq, ldw, Ws,
+                                                      ldws, bias, M, N, K, out, ldo, gate, tiles_m, tiles_n, MxQOut<false>{}));
     return mg_check_launch();
 }
 
@@ -408,13 +371,13 @@ extern "C" int mg_gemm_mxfp8_gelu_q(const uint8_t* Aq, int64_t lda, const uint8_
                                     int64_t ldw, const uint8_t* Ws, int64_t ldws, const float* bias, int64_t M, int N, int K,
                                     uint8_t* oq, int64_t ldoq, uint8_t* oscales, int64_t ldos, void* stream) {
     if (!oq || !oscales) return MG_ERR_ARG;
-    int rc = mx_gemm_check(Aq, lda, As, ldas, Wq, ldw, Ws, ldws, bias, M, N, K);
+    int rc = mx_gemm_check(Aq, lda, As, ldas, Wq, ldw, Ws, ldws, bias, nullptr, M, N, K);
     if (rc != MG_OK) return rc;
     if ((N % 32) || ldoq < N || ldos < N / 32 || (ldoq & 15) || (ldos & 3)) return MG_ERR_SHAPE;
     if (((uintptr_t)oq & 15) || ((uintptr_t)oscales & 3)) return MG_ERR_SHAPE;
     if (M == 0) return MG_OK;
     int tiles_m, tiles_n, nwg;
-    if ((rc = mx_gemm_grid(M, N, &tiles_m, &tiles_n, &nwg)) != MG_OK) return rc;
+    if ((rc = mg_gemm_persistent_grid(M, N, MX_BM, MX_BN, &tiles_m, &tiles_n, &nwg)) != MG_OK) return rc;
     const MxQOut<true> qo = {oscales, ldos};
     hipLaunchKernelGGL((gemm_mxfp8_kernel<MX_EPI_GELU_Q>), dim3((unsigned)nwg), dim3(MX_THREADS), 0, (hipStream_t)stream, Aq, lda,
                        As, ldas, Wq, ldw, Ws, ldws, bias, M, N, K, (void*)oq, ldoq, (const float*)nullptr, tiles_m, tiles_n, qo);

@@ -2,9 +2,9 @@
 // primitives (fragment read, counted wait, accumulator-pinned MFMA, LDS-DMA buffer load, M0 write) and the two epilogues shaped for the
 // CU's memory pipe (16-byte bf16 stores; fp32 rows through LDS).  Arithmetic = gemm_epilogue.h's, element for element.
 #pragma once
-#include "common.h"
 #include "gemm_epilogue.h"
-#include "../../include/moviigen_hip.h"
+#include "gemm_launch.h"
+#include "gemm_raster.h"
 
 #define V11_BM 256
 #define V11_BN 256
@@ -13,8 +13,6 @@
 #define V11_A_BYTES (V11_BM * V11_BK * 2)  // 32 KiB
 #define V11_W_BYTES (V11_BN * V11_BK * 2)  // 32 KiB
 #define V11_STAGE (V11_A_BYTES + V11_W_BYTES)
-
-typedef __attribute__((address_space(3))) void* v11_lptr_t;
 
 template <int OFF>
 MG_DEV void v11_rd(bf16x8_t& dst, unsigned addr) {
@@ -173,7 +171,7 @@ MG_DEV void v11_epilogue_rows(const f32x4_t (&acc)[8][8], char* __restrict__ sp,
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((float*)out + m_wave * ldo + n_wave, 0, 0x7fffffff, 0x00020000);
     const int row_bytes = (int)ldo * 4;
     const int voff = half * row_bytes + c8 * 16;
-    const unsigned wr = (unsigned)(uintptr_t)(v11_lptr_t)sp + r16 * 256 + (G & 1) * 8;
+    const unsigned wr = (unsigned)(uintptr_t)(mg_lptr_t)sp + r16 * 256 + (G & 1) * 8;
     char* const rd = sp + half * 256 + (c8 & 1) * 8;
     // The exchange is between the LANES of one wave: the hardware executes a wave's LDS instructions in order, but to the compiler
     // a lane's reads and another lane's writes are unrelated — without the compiler-level fences below it moved a read-back in front
@@ -264,7 +262,7 @@ MG_DEV void v11_epilogue_rows2(const f32x4_t (&acc)[8][8], char* __restrict__ sp
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((float*)out + m_wave * ldo + n_wave, 0, 0x7fffffff, 0x00020000);
     const int row_bytes = (int)ldo * 4;
     const int voff = half * row_bytes + c8 * 16;
-    const unsigned wr = (unsigned)(uintptr_t)(v11_lptr_t)sp + r16 * 256 + (G & 1) * 8;
+    const unsigned wr = (unsigned)(uintptr_t)(mg_lptr_t)sp + r16 * 256 + (G & 1) * 8;
     char* const rd = sp + half * 256 + (c8 & 1) * 8;
 #define V11_FENCE asm volatile("" ::: "memory")      // compiler-level: LDS exchange between the lanes of a wave; and loads stay in front of it
     // the bias BEFORE the residual stream starts: a load behind it would be waited for with vmcnt counting every older load too

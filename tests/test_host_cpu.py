@@ -57,6 +57,82 @@ def test_ab_library_switches_refuse_unknown_numbers():
             assert h.mg_attn_set_variant(v) != 0, v
 
 
+def _gemm_refusal_table():
+    """(entry point, overrides of a valid M == 0 call, expected return code).  Pointers are fabricated integers — 16-byte aligned
+    unless a row says otherwise — and never dereferenced: every row returns before the first HIP call."""
+    OK, ARG, SHAPE = 0, -1, -2
+    P = lambda i: 0x10000 * (i + 1)      # distinct, 16-byte aligned
+    bf16 = dict(A=P(0), lda=128, Wt=P(1), ldw=128, bias=P(2), M=0, N=64, K=128, epilogue=0, out=P(3), ldo=64, gate=P(4), stream=None)
+    mx = dict(Aq=P(0), lda=256, As=P(1), ldas=8, Wq=P(2), ldw=256, Ws=P(3), ldws=8, bias=P(4), M=0, N=64, K=256, epilogue=0,
+              out=P(5), ldo=64, gate=P(6), stream=None)
+    mxq = dict(Aq=P(0), lda=256, As=P(1), ldas=8, Wq=P(2), ldw=256, Ws=P(3), ldws=8, bias=P(4), M=0, N=64, K=256,
+               oq=P(5), ldoq=64, oscales=P(6), ldos=4, stream=None)
+    rows = []
+    add = lambda fn, base, code, **kw: rows.append((fn, dict(base, **kw), code, kw))
+    # ---- mg_gemm_bf16 ----
+    add('mg_gemm_bf16', bf16, OK)                                       # M == 0 behind every check
+    add('mg_gemm_bf16', bf16, OK, bias=None, gate=None)
+    for name in ('A', 'Wt', 'out'):
+        add('mg_gemm_bf16', bf16, ARG, **{name: None}, M=300)
+    for e in (-1, 4):
+        add('mg_gemm_bf16', bf16, ARG, epilogue=e, M=300)
+        add('mg_gemm_bf16', bf16, ARG, epilogue=e)                      # M == 0 does not hide it
+    for kw in (dict(M=-1), dict(N=0), dict(N=-64), dict(K=0), dict(K=-64), dict(K=96), dict(K=32), dict(lda=132), dict(ldw=129),
+               dict(ldo=66), dict(ldo=65), dict(A=P(0) + 8), dict(Wt=P(1) + 2), dict(out=P(3) + 4), dict(bias=P(2) + 4),
+               dict(gate=P(4) + 8)):
+        add('mg_gemm_bf16', bf16, SHAPE, **dict(dict(M=300), **kw))
+    add('mg_gemm_bf16', bf16, SHAPE, K=96)                              # ... nor a shape rule
+    add('mg_gemm_bf16', bf16, ARG, A=None, K=96, M=300)                 # precedence: an ARG rule and a SHAPE rule at once
+    add('mg_gemm_bf16', bf16, ARG, epilogue=4, A=P(0) + 8, M=300)
+    # ---- mg_gemm_mxfp8 ----
+    add('mg_gemm_mxfp8', mx, OK)
+    add('mg_gemm_mxfp8', mx, OK, bias=None, gate=None)
+    for name in ('Aq', 'As', 'Wq', 'Ws', 'out'):
+        add('mg_gemm_mxfp8', mx, ARG, **{name: None}, M=300)
+    for e in (-1, 4):
+        add('mg_gemm_mxfp8', mx, ARG, epilogue=e, M=300)
+        add('mg_gemm_mxfp8', mx, ARG, epilogue=e)
+    for kw in (dict(M=-1), dict(N=0), dict(N=-16), dict(K=0), dict(K=-128), dict(K=192), dict(K=64), dict(N=24, ldo=24), dict(N=72, ldo=72),
+               dict(lda=240), dict(ldw=128), dict(ldas=4), dict(ldws=7), dict(lda=264), dict(ldw=260), dict(ldas=10), dict(ldws=9),
+               dict(Aq=P(0) + 8), dict(Wq=P(2) + 4), dict(As=P(1) + 2), dict(Ws=P(3) + 1), dict(bias=P(4) + 8),
+               dict(ldo=48), dict(ldo=66), dict(out=P(5) + 8), dict(gate=P(6) + 4)):
+        add('mg_gemm_mxfp8', mx, SHAPE, **dict(dict(M=300), **kw))
+    add('mg_gemm_mxfp8', mx, SHAPE, K=192)
+    add('mg_gemm_mxfp8', mx, ARG, Ws=None, K=192, M=300)
+    add('mg_gemm_mxfp8', mx, ARG, epilogue=4, lda=240, M=300)
+    add('mg_gemm_mxfp8', mx, ARG, out=None, N=24, M=300)
+    # ---- mg_gemm_mxfp8_gelu_q ----
+    add('mg_gemm_mxfp8_gelu_q', mxq, OK)
+    add('mg_gemm_mxfp8_gelu_q', mxq, OK, bias=None)
+    for name in ('Aq', 'As', 'Wq', 'Ws', 'oq', 'oscales'):
+        add('mg_gemm_mxfp8_gelu_q', mxq, ARG, **{name: None}, M=300)
+    for kw in (dict(M=-1), dict(N=0), dict(K=0), dict(K=192), dict(N=24, ldoq=32), dict(N=48), dict(N=16, ldoq=16),
+               dict(lda=240), dict(ldw=128), dict(ldas=4), dict(ldws=7), dict(lda=264), dict(ldw=260), dict(ldas=10), dict(ldws=9),
+               dict(Aq=P(0) + 8), dict(Wq=P(2) + 4), dict(As=P(1) + 2), dict(Ws=P(3) + 1), dict(bias=P(4) + 8),
+               dict(ldoq=48), dict(ldos=1), dict(ldoq=72), dict(ldos=6), dict(oq=P(5) + 8), dict(oscales=P(6) + 2)):
+        add('mg_gemm_mxfp8_gelu_q', mxq, SHAPE, **dict(dict(M=300), **kw))
+    add('mg_gemm_mxfp8_gelu_q', mxq, SHAPE, N=48)
+    add('mg_gemm_mxfp8_gelu_q', mxq, ARG, oscales=None, K=192, M=300)
+    add('mg_gemm_mxfp8_gelu_q', mxq, ARG, Aq=None, N=48, M=300)
+    return rows
+
+
+def test_gemm_entry_points_refuse_bad_operands_with_the_documented_code():
+    """mg_gemm_bf16, mg_gemm_mxfp8 and mg_gemm_mxfp8_gelu_q validate their operands on the host before anything touches the GPU: a null operand
+    or an unknown epilogue is MG_ERR_ARG (-1) and wins over any shape fault in the same call; extents, K not a multiple of the k-tile, pitches
+    (16-byte rows, 4-byte scale rows, pitch >= extent for the MXFP8 operands and outputs), pointer alignment and the MXFP8 N % 16 / N % 32 rules
+    are MG_ERR_SHAPE (-2); M == 0 is MG_OK, but only for a call that is otherwise valid.  The codes are those of the entry points as they
+    were before the checks moved into csrc/gemm_launch.h; in the product and in the A/B library alike."""
+    from wan.backend import lib
+    rows = _gemm_refusal_table()
+    assert len(rows) > 100 and {c for _, _, c, _ in rows} == {0, -1, -2}
+    for handle in (lib.load(), lib.load_ab()):
+        for fn, args, want, what in rows:
+            got = getattr(handle, fn)(*args.values())
+            assert got == want, (fn, what, got, want)
+            assert want != 0 or args['M'] == 0      # nothing launchable in the table
+
+
 def test_product_never_imports_oracle():
     pkg = os.path.join(ROOT, 'moviigen1.1_amd')
     for dp, _, fns in os.walk(pkg):
