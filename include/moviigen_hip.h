@@ -53,6 +53,27 @@ int mg_ln_modulate(const float* x, int64_t ldx, int64_t rows, int dim, const flo
                    const float* shift, int add_one, float eps, int round_norm_bf16, void* out,
                    int out_f32, int64_t ldo, void* stream);
 
+/* Step cache (not the reference's arithmetic, opt-in).
+ *
+ * mg_step_resid_capture_f32: r[i] <- x[i] - xin[i], i < n, ONE fp32 subtract per element, behind the last block of a
+ * computed step (x the residual stream there, xin the stream as it stood behind the patch embedding).  With stats != NULL
+ * the same pass reduces stats[0] = sum |r_new[i] - r_old[i]| and stats[1] = sum |r_old[i]| (r_old = what r held): each
+ * difference and absolute value in fp32, widened and accumulated in fp64.  The grid is fixed, the per-workgroup fp64 sums go
+ * to `partials` (mg_step_resid_partials_bytes() bytes OWNED BY THE CALLER, 8-byte aligned, no initial value needed) and a
+ * second one-lane launch adds them in index order: the same inputs give the same 16 bytes, no atomics.  stats == NULL: no
+ * reduction, r is not read, partials is not touched (and may be NULL).
+ *   n >= 1, any value (scalar tail).  r, x, xin 16-byte aligned, stats 8-byte aligned: else MG_ERR_SHAPE.
+ *
+ * mg_resid_ln_modulate_f32: out = LN(x + r) * (1 + scale) + shift in fp32, x + r one fp32 add per element formed in
+ * registers: bit for bit mg_ln_modulate(add_one = 1, round_norm_bf16 = 0, out_f32 = 1) of the fp32 sum (the two kernels share
+ * one body), without the three passes over the stream (add, write, re-read).  x and r are only read.  The only full-size
+ * pass of a skipped step.  dim % 4 == 0, dim <= 8192, ld* % 4 == 0 and >= dim, all pointers 16-byte aligned. */
+int64_t mg_step_resid_partials_bytes(void);
+int mg_step_resid_capture_f32(float* r, const float* x, const float* xin, int64_t n, double* stats, double* partials,
+                              void* stream);
+int mg_resid_ln_modulate_f32(const float* x, int64_t ldx, const float* r, int64_t ldr, int64_t rows, int dim,
+                             const float* scale, const float* shift, float eps, float* out, int64_t ldo, void* stream);
+
 /* WanRMSNorm over the whole `dim` vector (fp32 math, result rounded to bf16, then * weight in
  * fp32) and optional 3-axis RoPE on adjacent pairs, output bf16.
  * Replaces wan/modules/model.py:70-86 (+:139-140, :168-169) and rope_apply model.py:39-67 /

@@ -28,12 +28,13 @@ struct LnMxOut<true> {
     int64_t lds;
 };
 
-template <int MAXV, bool MX = false>
-__global__ __launch_bounds__(NT) void ln_modulate_kernel(
-    const float* __restrict__ x, int64_t ldx, int64_t rows, int dim, const float* __restrict__ scale,
-    const float* __restrict__ shift, int add_one, float eps, int do_round, void* __restrict__ out,
-    int out_f32, int64_t ldo, LnMxOut<MX> mx) {
-    __shared__ float red[NT / 64];
+// The kernel's whole body is ln_modulate_rows, shared by the two entry kernels below, so that mg_resid_ln_modulate_f32 — RES: a row is
+// x + r, one fp32 add per element, formed as it is loaded — reduces and normalises in exactly the order mg_ln_modulate does.
+template <int MAXV, bool MX, bool RES>
+MG_DEV void ln_modulate_rows(
+    const float* __restrict__ x, int64_t ldx, const float* __restrict__ res, int64_t ldr, int64_t rows, int dim,
+    const float* __restrict__ scale, const float* __restrict__ shift, int add_one, float eps, int do_round, void* __restrict__ out,
+    int out_f32, int64_t ldo, LnMxOut<MX> mx, float* red) {
     const int nv = dim >> 2;
     const float inv_dim = 1.f / (float)dim;
     for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
@@ -45,6 +46,10 @@ __global__ __launch_bounds__(NT) void ln_modulate_kernel(
             const int c = threadIdx.x + i * NT;
             if (c < nv) {
                 v[i] = xr[c];
+                if constexpr (RES) {
+                    const float4 rv = ((const float4*)(res + row * ldr))[c];
+                    v[i].x += rv.x; v[i].y += rv.y; v[i].z += rv.z; v[i].w += rv.w;
+                }
                 s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
             } else {
                 v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -108,6 +113,24 @@ __global__ __launch_bounds__(NT) void ln_modulate_kernel(
     }
 }
 
+template <int MAXV, bool MX = false>
+__global__ __launch_bounds__(NT) void ln_modulate_kernel(
+    const float* __restrict__ x, int64_t ldx, int64_t rows, int dim, const float* __restrict__ scale,
+    const float* __restrict__ shift, int add_one, float eps, int do_round, void* __restrict__ out,
+    int out_f32, int64_t ldo, LnMxOut<MX> mx) {
+    __shared__ float red[NT / 64];
+    ln_modulate_rows<MAXV, MX, false>(x, ldx, nullptr, 0, rows, dim, scale, shift, add_one, eps, do_round, out, out_f32, ldo, mx, red);
+}
+
+// out = LN(x + r) * (1 + scale) + shift in fp32; x is only read
+template <int MAXV>
+__global__ __launch_bounds__(NT) void resid_ln_modulate_kernel(
+    const float* __restrict__ x, int64_t ldx, const float* __restrict__ r, int64_t ldr, int64_t rows, int dim,
+    const float* __restrict__ scale, const float* __restrict__ shift, float eps, float* __restrict__ out, int64_t ldo) {
+    __shared__ float red[NT / 64];
+    ln_modulate_rows<MAXV, false, true>(x, ldx, r, ldr, rows, dim, scale, shift, 1, eps, 0, out, 1, ldo, LnMxOut<false>{}, red);
+}
+
 extern "C" int mg_ln_modulate(const float* x, int64_t ldx, int64_t rows, int dim, const float* scale,
                               const float* shift, int add_one, float eps, int round_norm_bf16,
                               void* out, int out_f32, int64_t ldo, void* stream) {
@@ -127,6 +150,26 @@ extern "C" int mg_ln_modulate(const float* x, int64_t ldx, int64_t rows, int dim
     else
         hipLaunchKernelGGL(ln_modulate_kernel<8>, dim3(grid), dim3(NT), 0, st, x, ldx, rows, dim, scale,
                            shift, add_one, eps, round_norm_bf16, out, out_f32, ldo, LnMxOut<false>{});
+    return mg_check_launch();
+}
+
+extern "C" int mg_resid_ln_modulate_f32(const float* x, int64_t ldx, const float* r, int64_t ldr, int64_t rows, int dim,
+                                       const float* scale, const float* shift, float eps, float* out, int64_t ldo, void* stream) {
+    if (rows == 0) return MG_OK;
+    if (!x || !r || !out) return MG_ERR_ARG;
+    if (dim <= 0 || (dim & 3) || dim > 8192 || (ldx & 3) || (ldr & 3) || (ldo & 3) || ldx < dim || ldr < dim || ldo < dim) return MG_ERR_SHAPE;
+    if ((((uintptr_t)x | (uintptr_t)r | (uintptr_t)out) & 15) || (scale && ((uintptr_t)scale & 15)) || (shift && ((uintptr_t)shift & 15)))
+        return MG_ERR_SHAPE;
+    if (rows < 0) return MG_ERR_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = (int)(rows < 65536 * 4 ? rows : 65536 * 4);
+    const int nv = dim >> 2;
+    if (nv <= 2 * NT)
+        hipLaunchKernelGGL(resid_ln_modulate_kernel<2>, dim3(grid), dim3(NT), 0, st, x, ldx, r, ldr, rows, dim, scale, shift, eps, out, ldo);
+    else if (nv <= 5 * NT)
+        hipLaunchKernelGGL(resid_ln_modulate_kernel<5>, dim3(grid), dim3(NT), 0, st, x, ldx, r, ldr, rows, dim, scale, shift, eps, out, ldo);
+    else
+        hipLaunchKernelGGL(resid_ln_modulate_kernel<8>, dim3(grid), dim3(NT), 0, st, x, ldx, r, ldr, rows, dim, scale, shift, eps, out, ldo);
     return mg_check_launch();
 }
 
@@ -627,6 +670,106 @@ extern "C" int mg_gate_residual_f32(float* x, int64_t ldx, const uint16_t* y, in
     if (g > 16384) g = 16384;
     hipLaunchKernelGGL(gate_residual_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy, gate, rows,
                        dim / 4);
+    return mg_check_launch();
+}
+
+// ---------------------------------------------------------------------------------------------
+// step cache: r <- x - xin behind the last block of a computed step, and in the same pass the two sums the
+// calibration tool asks for, sum |r_new - r_old| and sum |r_old|.  Differences in fp32, widened and accumulated in fp64 per lane.
+// The grid is FIXED (SR_GRID workgroups of NT lanes, whatever the device), a lane's elements and their order are a function of n
+// alone, a workgroup's lanes are added in a fixed tree and the SR_GRID partials in index order by one lane of a second launch:
+// same inputs, same 16 bytes.  No atomics.
+// ---------------------------------------------------------------------------------------------
+#define SR_GRID 1024
+#define SR_UNROLL 4
+
+MG_DEV double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <bool STATS>
+__global__ __launch_bounds__(NT) void step_resid_capture_kernel(float* __restrict__ r, const float* __restrict__ x,
+                                                                const float* __restrict__ xin, int64_t n, double* __restrict__ partials) {
+    __shared__ double red[2][NT / 64];
+    const int64_t nvec = n >> 2;
+    const int64_t stride = (int64_t)gridDim.x * NT;
+    double sd = 0.0, so = 0.0;
+    for (int64_t i0 = (int64_t)blockIdx.x * NT + threadIdx.x; i0 < nvec; i0 += stride * SR_UNROLL) {
+        f32x4_t a[SR_UNROLL], b[SR_UNROLL], o[SR_UNROLL];
+#pragma unroll
+        for (int u = 0; u < SR_UNROLL; ++u) {
+            const int64_t i = i0 + u * stride;
+            if (i < nvec) {
+                a[u] = ((const f32x4_t*)x)[i];
+                b[u] = ((const f32x4_t*)xin)[i];
+                if constexpr (STATS) o[u] = ((const f32x4_t*)r)[i];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < SR_UNROLL; ++u) {
+            const int64_t i = i0 + u * stride;
+            if (i < nvec) {
+                const f32x4_t d = a[u] - b[u];
+                if constexpr (STATS) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        sd += (double)fabsf(d[e] - o[u][e]);
+                        so += (double)fabsf(o[u][e]);
+                    }
+                }
+                ((f32x4_t*)r)[i] = d;
+            }
+        }
+    }
+    if (blockIdx.x == 0 && (int64_t)threadIdx.x < n - (nvec << 2)) {      // the scalar tail: n % 4 elements
+        const int64_t i = (nvec << 2) + threadIdx.x;
+        const float d = x[i] - xin[i];
+        if constexpr (STATS) {
+            const float o = r[i];
+            sd += (double)fabsf(d - o);
+            so += (double)fabsf(o);
+        }
+        r[i] = d;
+    }
+    if constexpr (STATS) {
+        sd = wave_sum_f64(sd);
+        so = wave_sum_f64(so);
+        const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+        if (l == 0) { red[0][w] = sd; red[1][w] = so; }
+        __syncthreads();
+        if (threadIdx.x < 2) {
+            double t = 0.0;
+#pragma unroll
+            for (int k = 0; k < NT / 64; ++k) t += red[threadIdx.x][k];
+            partials[2 * blockIdx.x + threadIdx.x] = t;
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void step_resid_finish_kernel(const double* __restrict__ partials, double* __restrict__ stats) {
+    if (threadIdx.x < 2) {      // lane 0: sum |r_new - r_old|, lane 1: sum |r_old| — each in index order
+        double t = 0.0;
+        for (int b = 0; b < SR_GRID; ++b) t += partials[2 * b + threadIdx.x];
+        stats[threadIdx.x] = t;
+    }
+}
+
+extern "C" int64_t mg_step_resid_partials_bytes(void) { return (int64_t)SR_GRID * 2 * sizeof(double); }
+
+extern "C" int mg_step_resid_capture_f32(float* r, const float* x, const float* xin, int64_t n, double* stats, double* partials,
+                                         void* stream) {
+    if (!r || !x || !xin || (stats && !partials)) return MG_ERR_ARG;
+    if (n < 1) return MG_ERR_SHAPE;
+    if ((((uintptr_t)r | (uintptr_t)x | (uintptr_t)xin) & 15) || ((uintptr_t)stats & 7) || (stats && ((uintptr_t)partials & 7))) return MG_ERR_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    if (stats) {
+        hipLaunchKernelGGL(step_resid_capture_kernel<true>, dim3(SR_GRID), dim3(NT), 0, st, r, x, xin, n, partials);
+        hipLaunchKernelGGL(step_resid_finish_kernel, dim3(1), dim3(64), 0, st, (const double*)partials, stats);
+    } else {
+        hipLaunchKernelGGL(step_resid_capture_kernel<false>, dim3(SR_GRID), dim3(NT), 0, st, r, x, xin, n, (double*)nullptr);
+    }
     return mg_check_launch();
 }
 

@@ -22,6 +22,9 @@ SIGNATURES = {
     'mg_version': [],
     'mg_abi_version': [],
     'mg_ln_modulate': [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_int, c_f32, c_int, c_vp, c_int, c_i64, c_vp],
+    'mg_step_resid_partials_bytes': [],
+    'mg_step_resid_capture_f32': [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
+    'mg_resid_ln_modulate_f32': [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp],
     'mg_rmsnorm_rope_bf16': [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_f32, c_int, c_vp, c_int, c_int,
                              c_int, c_i64, c_f32, c_vp],
     'mg_pack_kv_bf16': [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp],
@@ -95,7 +98,8 @@ SIGNATURES_AB = {
     'mg_gemm_debug_profile': [c_vp],
     'mg_gemm5_debug_profile': [c_vp],
 }
-_RESTYPE = {'mg_version': ctypes.c_char_p, 'mg_vae_attn_workspace_floats': ctypes.c_int64, 'mg_attn_workspace_bytes': ctypes.c_int64, 'mg_attn_w64_profile': None,
+_RESTYPE = {'mg_version': ctypes.c_char_p, 'mg_vae_attn_workspace_floats': ctypes.c_int64, 'mg_attn_workspace_bytes': ctypes.c_int64,
+            'mg_step_resid_partials_bytes': ctypes.c_int64, 'mg_attn_w64_profile': None,
             'mg_attn_w64_debug': None, 'mg_attn_w64_flag_counter': None, 'mg_gemm_debug_profile': None, 'mg_gemm5_debug_profile': None}
 DEFAULT_GEMM_VARIANT = 0   # mg_gemm_set_variant(0) = the product's rule by shape (A/B library)
 

@@ -38,6 +38,45 @@ def ln_modulate(x, scale, shift, add_one, eps, out, round_norm_bf16=False):
     return out
 
 
+def resid_ln_modulate(x, r, scale, shift, eps, out):
+    """out [rows, dim] fp32 = LN(x + r) * (1 + scale) + shift, x and r [rows, dim] fp32 (row strides free), only read: the bits of
+    ln_modulate(lincomb(x, r), scale, shift, True, eps, out) in one pass (the step cache's skipped step)."""
+    _chk(x, torch.float32, 'x'); _chk(r, torch.float32, 'r'); _chk(scale, torch.float32, 'scale'); _chk(shift, torch.float32, 'shift')
+    _chk(out, torch.float32, 'out')
+    if x.dim() != 2 or tuple(r.shape) != tuple(x.shape) or tuple(out.shape) != tuple(x.shape):
+        raise lib.MoviigenHipError(f'resid_ln_modulate shape mismatch x{tuple(x.shape)} r{tuple(r.shape)} out{tuple(out.shape)}')
+    rows, dim = x.shape
+    for name, t in (('scale', scale), ('shift', shift)):
+        if t is not None and t.numel() != dim:
+            raise lib.MoviigenHipError(f'resid_ln_modulate: {name} must have {dim} elements, got {t.numel()}')
+    lib.call('mg_resid_ln_modulate_f32', _p(x), x.stride(0), _p(r), r.stride(0), rows, dim, _p(scale), _p(shift), float(eps), _p(out),
+             out.stride(0), _st())
+    return out
+
+
+def step_resid_partials(device):
+    """the caller-owned scratch of step_resid_capture(stats=...): mg_step_resid_partials_bytes() bytes as fp64, no initial value needed"""
+    return torch.empty(int(lib.load().mg_step_resid_partials_bytes()) // 8, dtype=torch.float64, device=device)
+
+
+def step_resid_capture(r, x, xin, stats=None, partials=None):
+    """r <- x - xin (contiguous fp32 tensors of equal size, r IN PLACE).  stats: fp64 [2] receiving (sum |r_new - r_old|, sum |r_old|),
+    r_old = what r held — deterministic (fixed grid, fixed order); it needs `partials` (step_resid_partials).  None: no reduction."""
+    for name, t in (('r', r), ('x', x), ('xin', xin)):
+        _chk(t, torch.float32, name)
+        if t is None or not t.is_contiguous():
+            raise lib.MoviigenHipError(f'{name} must be a contiguous fp32 tensor')
+    if x.numel() != r.numel() or xin.numel() != r.numel():
+        raise lib.MoviigenHipError(f'step_resid_capture size mismatch r{tuple(r.shape)} x{tuple(x.shape)} xin{tuple(xin.shape)}')
+    if stats is not None:
+        _chk(stats, torch.float64, 'stats'); _chk(partials, torch.float64, 'partials')
+        if stats.numel() < 2 or not stats.is_contiguous() or partials is None or not partials.is_contiguous() \
+                or partials.numel() * 8 < int(lib.load().mg_step_resid_partials_bytes()):
+            raise lib.MoviigenHipError('step_resid_capture: stats must be fp64 [2] and partials step_resid_partials(device)')
+    lib.call('mg_step_resid_capture_f32', _p(r), _p(x), _p(xin), r.numel(), _p(stats), _p(partials) if stats is not None else None, _st())
+    return r
+
+
 ATTN_LOG2E = 1.4426950408889634
 
 

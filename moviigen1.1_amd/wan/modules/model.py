@@ -22,6 +22,7 @@ K/V projections) is computed once per prompt and cached — identical values, 10
 
 There is no torch fallback: without the HIP library (or a GPU) forward() raises.
 """
+import contextlib
 import json
 import math
 import os
@@ -262,6 +263,8 @@ class WanModel(nn.Module):
         self._ctx_cache = {}
         self._lora = []                 # load_lora: (name, strength) of the adapters merged into the weights
         self._lora_base = None          # ... and the touched weights as they were (keep_base=True), for unload_lora
+        self._step_mode = None          # step_cache(): ('compute' | 'skip', stats) while the scope is open
+        self.step_cache_stats = {}      # stats=True: context key -> (sum |r_new - r_old|, sum |r_old|) of its last computed step
 
     @property
     def freqs(self):
@@ -340,6 +343,7 @@ class WanModel(nn.Module):
         self._packed = None
         self._mx = None
         self._ctx_cache = {}
+        self.drop_step_cache()          # residuals of other weights are not residuals of these
 
     def _apply(self, fn, recurse=True):
         out = super()._apply(fn, recurse)
@@ -470,8 +474,78 @@ class WanModel(nn.Module):
         if precision == 'mxfp8' and getattr(self, '_shards', None) is not None:
             raise NotImplementedError("set_gemm_precision('mxfp8') needs resident weights: block-sharded weights (wan.distributed.fsdp) "
                                       'are gathered in bf16 per block and are not quantised')
+        if precision != self.gemm_precision:
+            self.drop_step_cache()
         self.gemm_precision = precision
         return self
+
+    # ------------------------------------------------------------------------------------------
+    # step cache: skip the blocks of a step and add the residual of the last computed one again
+    # ------------------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def step_cache(self, mode, stats=False):
+        """`with model.step_cache('compute' | 'skip', stats=False):` — how the forwards of the scope run.  NOT the reference's arithmetic:
+        an opt-in like set_gemm_precision('mxfp8'); outside a scope nothing of it runs.
+        'compute': the forward as always (the same bits), plus: the residual stream as it stands behind the patch embedding is kept
+            (ws['xin']) and behind the last block r = x - xin goes to the residual buffer of this (workspace shape, context): fp32
+            [L, dim], one per context, in the workspace.  stats=True also fills step_cache_stats[context key] =
+            (sum |r - r_old|, sum |r_old|) — a host read per forward, for tools/step_cache_calibrate.py only; per-rank sums under SP.
+        'skip': patch and time embedding as always, NO block (no weight gather, no exchange), then head(LN(x + r)) with the context's
+            residual; RuntimeError when this (workspace shape, context) has none.
+        Whatever invalidates the packed weights (load_state_dict, .to(), load_lora / unload_lora, set_gemm_precision) and a change of
+        the workspace shape drop the residuals; drop_step_cache() frees them (3 x [L, dim] fp32: xin and two residuals under CFG)."""
+        if mode not in ('compute', 'skip'):
+            raise ValueError(f"step_cache mode must be 'compute' or 'skip', got {mode!r}")
+        prev, self._step_mode = self._step_mode, (mode, bool(stats))
+        try:
+            yield self
+        finally:
+            self._step_mode = prev
+
+    def drop_step_cache(self):
+        """free the step cache's buffers (xin, the residuals, the reduction scratch) and forget the stats"""
+        for ws in getattr(self, '_ws', {}).values():
+            for k in ('xin', 'resid', 'resid_stats'):
+                ws.pop(k, None)
+        self.step_cache_stats = {}
+
+    @staticmethod
+    def _ctx_key(ctx):
+        """what names a prompt tensor: the key of _context()'s cache and of the step cache's residuals"""
+        return (ctx.data_ptr(), tuple(ctx.shape), ctx._version)
+
+    def _step_resid(self, ws, ctx, create):
+        """the residual buffer of this workspace for prompt tensor `ctx` (zeros when new: r_old of a first computed step), or None"""
+        key = self._ctx_key(ctx)
+        table = ws.setdefault('resid', {})
+        hit = table.get(key)
+        if hit is None and create:
+            if len(table) >= 4:         # as _context(): prompts come and go, [L, dim] fp32 each does not pile up
+                table.pop(next(iter(table)))
+            hit = table[key] = (ctx, torch.zeros_like(ws['x']))      # (ctx is kept alive so that its data_ptr stays unique)
+        return None if hit is None else hit[1]
+
+    def time_embeddings(self, timesteps):
+        """(e [N, dim], e0 [N, 6 dim]) fp32 of the N timesteps by the forward's own kernels (reference model.py:541-545): what the
+        step-cache plan is a function of (wan/utils/step_cache.py)."""
+        dev, d = self.patch_embedding.weight.device, self.dim
+        tt = timesteps.reshape(-1).to(dev)
+        if tt.dtype not in (torch.int64, torch.float32, torch.float64):
+            tt = tt.to(torch.float32)
+        n = tt.numel()
+        f32 = dict(dtype=torch.float32, device=dev)
+        sin, e1 = torch.empty(1, self.freq_dim, **f32), torch.empty(d, **f32)
+        e, e0 = torch.empty(n, d, **f32), torch.empty(n, 6 * d, **f32)
+        for i in range(n):
+            self._time_embedding(tt[i:i + 1], sin, e1, e[i], e0[i])
+        return e, e0
+
+    def _time_embedding(self, tt, sin, e1, e, e0):
+        ops.sinusoid_embed(tt, self.freq_dim, sin)
+        te, tp = self.time_embedding, self.time_projection['1']
+        ops.gemv(te['0'].weight, te['0'].bias, sin, e1)
+        ops.gemv(te['2'].weight, te['2'].bias, e1, e, silu_in=True)
+        ops.gemv(tp.weight, tp.bias, e, e0, silu_in=True)
 
     def _mx_layers(self):
         """per block {site: (e4m3 bytes [N, K], scale bytes [N, K/32])} for the sites MXFP8_SITES enables"""
@@ -570,7 +644,7 @@ class WanModel(nn.Module):
         """-> (ctx, emb [text_len, dim] bf16, layers): `layers[i]` is block i's cross-attention (K, V) — filled by
         _cross_kv the first time block i runs for this prompt, i.e. while that block's weights are at hand anyway
         (block-sharded mode: no extra all-gather sweep over the 28 GB of weights per new prompt)."""
-        key = (ctx.data_ptr(), tuple(ctx.shape), ctx._version)
+        key = self._ctx_key(ctx)
         hit = self._ctx_cache.get(key)
         if hit is not None:
             return hit
@@ -726,9 +800,23 @@ class WanModel(nn.Module):
         x = ws['x']
 
         reuse = share == 'reuse'
-        if share == 'save' and 'x0' not in ws:
-            ws['x0'] = torch.empty_like(x)
-        assert not reuse or 'x0' in ws, "share='reuse' follows a share='save' forward of the same latent and t"
+        step, step_stats = self._step_mode or (None, False)
+        resid = None
+        if step == 'skip':
+            # 'reuse' finds x as the 'save' half embedded it: a skipped forward reads the stream and never writes it
+            resid = self._step_resid(ws, ctx, create=False)
+            if resid is None:
+                raise RuntimeError("step_cache('skip'): no residual for this sequence length and context — a step_cache('compute') forward "
+                                   'of the same context has to come first (weight changes and drop_step_cache() drop the residuals)')
+        else:
+            if share == 'save' and 'x0' not in ws:
+                ws['x0'] = torch.empty_like(x)
+            assert not reuse or 'x0' in ws, "share='reuse' follows a share='save' forward of the same latent and t"
+        if step == 'compute':
+            if 'xin' not in ws:
+                assert not reuse, "share='reuse' follows a share='save' forward in the same step_cache scope"
+                ws['xin'] = torch.empty_like(x)
+            resid = self._step_resid(ws, ctx, create=True)
 
         # patch embedding (model.py:529-531): bf16 result, residual stream kept in fp32 storage
         if reuse:
@@ -743,18 +831,20 @@ class WanModel(nn.Module):
             ops.gemm(ws['tok'][:n_valid], pk['patch_w'], self.patch_embedding.bias, ops.BIAS_F32, x[:n_valid])
         if n_valid < L and not reuse:
             x[n_valid:].zero_()                          # rows padded AFTER the patch embedding (no bias), :704-706
+        if step == 'compute' and not reuse:
+            ws['xin'].copy_(x)                           # ('reuse': the 'save' half's copy — the same latent, the same data)
 
         # time embedding (model.py:541-545), fp32
         tt = t.reshape(1).to(dev)
         if tt.dtype not in (torch.int64, torch.float32, torch.float64):
             tt = tt.to(torch.float32)
-        ops.sinusoid_embed(tt, self.freq_dim, ws['sin'])
-        te, tp = self.time_embedding, self.time_projection['1']
-        ops.gemv(te['0'].weight, te['0'].bias, ws['sin'], ws['e1'])
-        ops.gemv(te['2'].weight, te['2'].bias, ws['e1'], ws['e'], silu_in=True)
-        ops.gemv(tp.weight, tp.bias, ws['e'], ws['e0'], silu_in=True)
-        ops.add_rows(pk['modulation'], ws['e0'], ws['mod'], 6)                       # model.py:292-295
+        self._time_embedding(tt, ws['sin'], ws['e1'], ws['e'], ws['e0'])
         ops.add_rows(self.head.modulation.data.reshape(2, d), ws['e'].reshape(1, d), ws['hmod'], 1)
+        if step == 'skip':
+            # no block runs: the residual the blocks added at this context's last computed step is added again, inside the head's LayerNorm
+            ops.resid_ln_modulate(x, resid, ws['hmod'][1], ws['hmod'][0], eps, ws['hf'])
+            return self._head_out(ws, grid, (F, H, W), dev)
+        ops.add_rows(pk['modulation'], ws['e0'], ws['mod'], 6)                       # model.py:292-295
 
         _, ctx_emb, ctx_layers = self._context(ctx)
         rope = self._rope_tab(grid, dev)
@@ -817,15 +907,30 @@ class WanModel(nn.Module):
                 self._linear('ffn.0', ws['h'], qd, lw, mx, blk.ffn['0'].bias, ops.BIAS_GELU_BF16, ws['u'], quantised=hq)
             self._linear('ffn.2', ws['u'], qf, lw, mx, blk.ffn['2'].bias, ops.GATE_RESID_F32, x, gate=m[5], quantised=uq)
 
+        if step == 'compute':                            # what the blocks added to the stream, for the skipped steps that follow
+            if step_stats:
+                if 'resid_stats' not in ws:
+                    ws['resid_stats'] = (torch.empty(2, dtype=torch.float64, device=dev), ops.step_resid_partials(dev))
+                st, part = ws['resid_stats']
+                ops.step_resid_capture(resid, x, ws['xin'], st, part)
+                self.step_cache_stats[self._ctx_key(ctx)] = tuple(st.tolist())
+            else:
+                ops.step_resid_capture(resid, x, ws['xin'])
+
         # head (model.py:333-343): fp32 end to end
         ops.ln_modulate(x, ws['hmod'][1], ws['hmod'][0], True, eps, ws['hf'])
+        return self._head_out(ws, grid, (F, H, W), dev)
+
+    def _head_out(self, ws, grid, fhw, dev):
+        """head Linear on ws['hf'], the SP all-gather and unpatchify (model.py:342, :561-565)"""
+        P = self.sp_size
         ops.head_gemm(ws['hf'], self.head.head.weight, self.head.head.bias, ws['y'])
         y = ws['y']
         if P > 1:
             from ..distributed import ulysses
             y = ulysses.all_gather_seq(ws['y'], self.sp_group, P)                   # get_sp_group().all_gather
-        out = torch.empty(self.out_dim, F, H, W, dtype=torch.float32, device=dev)
-        ops.unpatchify(y, self.out_dim, grid[0], grid[1], grid[2], ph, pw, out)
+        out = torch.empty(self.out_dim, *fhw, dtype=torch.float32, device=dev)
+        ops.unpatchify(y, self.out_dim, grid[0], grid[1], grid[2], self.patch_size[1], self.patch_size[2], out)
         return out
 
     def forward(self, x, t, context, seq_len, clip_fea=None, y=None):

@@ -10,6 +10,7 @@ created from `checkpoint_dir/config.t5_checkpoint` as in the reference when that
 `text_encoder=` injects any callable with T5EncoderModel's contract (prompt list, device) -> list
 of `[len<=512, 4096]` tensors, and `input_prompt` / `n_prompt` may also be pre-computed embeddings.
 """
+import contextlib
 import gc
 import logging
 import math
@@ -25,6 +26,7 @@ from .modules.model import WanModel
 from .modules.vae import WanVAE
 from .utils.fm_solvers import FlowDPMSolverMultistepScheduler, get_sampling_sigmas, retrieve_timesteps
 from .utils.fm_solvers_unipc import FlowUniPCMultistepScheduler
+from .utils.step_cache import resolve_plan
 
 
 def v2v_steps(sampling_steps, strength):
@@ -40,7 +42,7 @@ class WanT2V:
 
     def __init__(self, config, checkpoint_dir, device_id=0, rank=0, t5_fsdp=False, dit_fsdp=False, use_usp=False,
                  t5_cpu=False, text_encoder=None, model=None, vae=None, cfg_parallel=False, vae_parallel=False, use_ring=False, sp_degrees=None,
-                 dit_gemm='bf16', lora=None, lora_strength=1.0):
+                 dit_gemm='bf16', step_cache=None, lora=None, lora_strength=1.0):
         self.device = torch.device(f'cuda:{device_id}')
         self.config = config
         self.rank = rank
@@ -109,6 +111,9 @@ class WanT2V:
         if dit_gemm != 'bf16':      # the default leaves a caller-supplied `model=` object untouched
             self.model.set_gemm_precision(dit_gemm)
         self.sample_neg_prompt = config.sample_neg_prompt
+        # the object's default for generate(step_cache=): None = every step runs the blocks (the reference's loop)
+        self.step_cache = step_cache
+        self.last_step_plan = self.last_step_timesteps = None
 
     def _encode(self, prompt):
         if torch.is_tensor(prompt):
@@ -147,10 +152,26 @@ class WanT2V:
         assert torch.isfinite(z0).all().item(), 'the encoded init_video is not finite'
         return ops.lincomb(torch.empty_like(noise), [(z0, 1.0 - sigma), (noise, sigma)])
 
+    def _guidance_pair(self, latent, t, context, context_null, seq_len):
+        """(cond, uncond) noise predictions of one denoising step"""
+        pair = getattr(self.model, 'forward_pair', None)
+        if self.cfgp is None and pair is not None:
+            # both branches in one call: what they share (everything in front of block 0's cross-attention) is computed once,
+            # the results are those of the two calls below bit for bit (WanModel.forward_pair)
+            cond, uncond = pair([latent], t, context, context_null, seq_len)
+            return cond[0], uncond[0]
+        if self.cfgp is None:      # a model object without forward_pair: the reference's two calls (text2video.py:237-240)
+            cond = self.model([latent], t=t, context=context, seq_len=seq_len)[0]
+            uncond = self.model([latent], t=t, context=context_null, seq_len=seq_len)[0]
+            return cond, uncond
+        # this half's branch only, then swap predictions with the partner rank
+        mine = self.model([latent], t=t, context=context_null if self.cfgp.branch else context, seq_len=seq_len)[0]
+        return self.cfgp.exchange(mine)
+
     def generate(self, input_prompt, size=(1280, 720), frame_num=81, shift=5.0, sample_solver='unipc',
                  sampling_steps=50, guide_scale=5.0, n_prompt="", seed=-1, offload_model=True,
-                 noise=None, callback=None, init_video=None, strength=1.0):
-        """The reference's `generate` (text2video.py:114-271), plus a video-to-video start that is NOT part of the reference:
+                 noise=None, callback=None, step_cache=None, init_video=None, strength=1.0):
+        """The reference's `generate` (text2video.py:114-271), plus a video-to-video start and a step cache that are NOT part of the reference:
 
         init_video: an existing clip to start from instead of pure noise — uint8 RGB frames [T, H0, W0, 3] of any size (tensor or array;
             resized to cover `size` and centre-cropped on the GPU, ops.video_from_u8) or a float clip [3, T, H, W] in [-1, 1] already at
@@ -159,7 +180,15 @@ class WanT2V:
             same bits everywhere, no collective), the start latent is (1 - sigma) z0 + sigma noise at the sigma of schedule index i0 and the
             loop runs the steps i0 .. sampling_steps - 1; `callback(i, latent)` gets these schedule indices.  At strength 1 the start is
             0 z0 + 1 noise: the result is bit-identical to the call without init_video and the same noise.
-        Without init_video nothing changes, call for call."""
+        Without init_video nothing changes, call for call.
+
+        step_cache (default: the object's, WanT2V(step_cache=); None = off): skip the DiT blocks of some steps and add the residual of the
+            last computed step again (WanModel.step_cache; TeaCache's rule on the time embedding) — a float threshold,
+            a dict of wan.utils.step_cache.step_cache_plan's arguments (thresh, coefficients, source, keep_first, keep_last), or an
+            explicit plan: one bool per schedule index, True = compute.  The plan is a function of the timesteps and the weights only:
+            known before the loop, the same on every rank and for both guidance branches.  The first step that runs is always computed.
+            `self.last_step_plan` holds the plan of the last call (None without a step cache); the residuals are dropped when the loop ends.
+            Threshold 0 and an all-True plan give the bits of step_cache=None."""
         n_run, i0 = v2v_steps(sampling_steps, strength)
         if init_video is None and i0:
             raise ValueError('strength < 1 needs init_video: there is nothing to start from')
@@ -203,26 +232,26 @@ class WanT2V:
             if next(self.model.parameters()).device != self.device:     # only after a real offload (a no-op move would
                 self.model.to(self.device)                               # still drop the fused-weight views: 28 GB re-packed)
             noise_pred = torch.empty_like(latent)
+            plan, plan_stats = resolve_plan(self.step_cache if step_cache is None else step_cache, self.model, timesteps, i0)
+            self.last_step_plan = plan
+            self.last_step_timesteps = timesteps if plan is not None else None     # what the plan was made of (tools/step_cache_calibrate.py)
             for i, t_host in enumerate(timesteps_host[i0:], start=i0):
                 t = timesteps[i:i + 1]
-                pair = getattr(self.model, 'forward_pair', None)
-                if self.cfgp is None and pair is not None:
-                    # both branches in one call: what they share (everything in front of block 0's cross-attention) is computed once,
-                    # the results are those of the two calls below bit for bit (WanModel.forward_pair)
-                    cond, uncond = pair([latent], t, context, context_null, seq_len)
-                    cond, uncond = cond[0], uncond[0]
-                elif self.cfgp is None:      # a model object without forward_pair: the reference's two calls (text2video.py:237-240)
-                    cond = self.model([latent], t=t, context=context, seq_len=seq_len)[0]
-                    uncond = self.model([latent], t=t, context=context_null, seq_len=seq_len)[0]
-                else:   # this half's branch only, then swap predictions with the partner rank
-                    mine = self.model([latent], t=t, context=context_null if self.cfgp.branch else context,
-                                      seq_len=seq_len)[0]
-                    cond, uncond = self.cfgp.exchange(mine)
+                step_mode = contextlib.nullcontext()
+                if plan is not None and not plan[i]:
+                    step_mode = self.model.step_cache('skip')
+                elif plan is not None and (plan_stats or (i + 1 < len(plan) and not plan[i + 1])):
+                    # a computed step keeps its residual only when the next step adds it again (or the calibration tool asked for the sums)
+                    step_mode = self.model.step_cache('compute', stats=plan_stats)
+                with step_mode:
+                    cond, uncond = self._guidance_pair(latent, t, context, context_null, seq_len)
                 ops.cfg_combine(noise_pred, uncond, cond, guide_scale)
                 latent = sample_scheduler.step(noise_pred.unsqueeze(0), t_host, latent.unsqueeze(0),
                                                return_dict=False, generator=seed_g)[0].squeeze(0)
                 if callback is not None:
                     callback(i, latent)
+            if plan is not None:
+                self.model.drop_step_cache()
             x0 = [latent]
             offloaded = False
             if offload_model:

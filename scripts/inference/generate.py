@@ -12,7 +12,11 @@ must equal the world size as in the reference), `--use_prompt_extend` is not bui
 `--t5_fsdp` / `--t5_cpu` are accepted (the 9.4 GB encoder is simply replicated on the GPU).  Extra:
 `--cfg_parallel`, `--vae_parallel` (this engine's multi-GPU layouts),
 `--init_video FILE` / `--strength F` (a video-to-video start, `WanT2V.generate(init_video=, strength=)`),
-`--lora PATH[:STRENGTH]` (repeatable: LoRA adapters merged into the DiT weights on the device, `WanModel.load_lora`) and
+`--lora PATH[:STRENGTH]` (repeatable: LoRA adapters merged into the DiT weights on the device, `WanModel.load_lora`),
+`--step_cache THRESH` / `--step_cache_coefficients a,b,c,d,e` / `--step_cache_keep FIRST,LAST` (opt-in step cache,
+`WanT2V.generate(step_cache=)`: steps whose time embedding has barely moved skip the DiT blocks and add the last computed step's
+residual again; the coefficients come from `tools/step_cache_calibrate.py` on the real checkpoint — no threshold is recommended
+without that calibration) and
 `--prompt_embeds FILE` (a torch file {'prompt': [len,4096], 'negative': [len,4096]} instead of running
 umT5 — for boxes without the tokenizer files)."""
 import argparse
@@ -78,6 +82,14 @@ FLAGS = [
     ('--lora', dict(type=str, action='append', default=None, metavar='PATH[:STRENGTH]',
                     help='a LoRA adapter (.safetensors: PEFT / diffusers or kohya / ComfyUI key names) merged into the DiT weights before sampling, '
                          'with an optional strength (default 1.0); may be given several times: all adapters are merged in one step, with one rounding.')),
+    ('--step_cache', dict(type=float, default=None, metavar='THRESH',
+                          help='opt-in step cache (TeaCache rule on the time embedding): a step is skipped while the accumulated predicted change since the '
+                               'last computed step stays below THRESH (0 = every step computed). Not the reference arithmetic; off by default.')),
+    ('--step_cache_coefficients', dict(type=str, default=None, metavar='a,b,c,d,e',
+                                       help='with --step_cache: polynomial (highest power first, numpy.polyval) mapping the embedding distance to the '
+                                            'predicted output change, as tools/step_cache_calibrate.py prints it; default 0,0,0,1,0 (the raw distance).')),
+    ('--step_cache_keep', dict(type=str, default=None, metavar='FIRST,LAST',
+                               help='with --step_cache: always compute the first FIRST and the last LAST steps (default 1,1).')),
     ('--prompt_embeds', dict(type=str, default=None, help="torch file {'prompt','negative'} of umT5 embeddings, replaces the text encoder.")),
 ]
 
@@ -92,6 +104,32 @@ def _lora_arg(arg):
         except ValueError:
             pass
     return arg, 1.0
+
+
+def _step_cache_spec(args):
+    """the three --step_cache* flags -> WanT2V.generate's `step_cache` argument (None without --step_cache)"""
+    if args.step_cache is None:
+        assert args.step_cache_coefficients is None and args.step_cache_keep is None, \
+            '--step_cache_coefficients / --step_cache_keep need --step_cache'
+        return None
+    assert args.step_cache >= 0.0, f'--step_cache must be >= 0, got {args.step_cache}'      # (also refuses nan)
+    spec = dict(thresh=args.step_cache)
+    if args.step_cache_coefficients is not None:
+        try:
+            coef = [float(c) for c in args.step_cache_coefficients.split(',')]
+        except ValueError:
+            coef = []
+        assert coef and all(c == c and abs(c) != float('inf') for c in coef), \
+            f'--step_cache_coefficients must be finite numbers a,b,c,... (highest power first), got {args.step_cache_coefficients!r}'
+        spec['coefficients'] = coef
+    if args.step_cache_keep is not None:
+        try:
+            keep = [int(k) for k in args.step_cache_keep.split(',')]
+        except ValueError:
+            keep = []
+        assert len(keep) == 2 and min(keep) >= 0, f'--step_cache_keep must be FIRST,LAST (two integers >= 0), got {args.step_cache_keep!r}'
+        spec['keep_first'], spec['keep_last'] = keep
+    return spec
 
 
 def _validate_args(args):
@@ -110,6 +148,7 @@ def _validate_args(args):
     assert 0.0 < args.strength <= 1.0, f'--strength must be in (0, 1], got {args.strength}'
     assert args.init_video is not None or args.strength == 1.0, '--strength needs --init_video'
     args.lora = [_lora_arg(a) for a in args.lora or []]
+    args.step_cache_spec = _step_cache_spec(args)
     assert args.size in SUPPORTED_SIZES[args.task], \
         f"Unsupport size {args.size} for task {args.task}, supported sizes are: {', '.join(SUPPORTED_SIZES[args.task])}"
 
@@ -194,7 +233,10 @@ def generate(args):
     video = pipe.generate(prompt, size=SIZE_CONFIGS[args.size], frame_num=args.frame_num, shift=args.sample_shift,
                           sample_solver=args.sample_solver, sampling_steps=args.sample_steps,
                           guide_scale=args.sample_guide_scale, n_prompt=n_prompt, seed=args.base_seed,
-                          offload_model=args.offload_model, **v2v)
+                          offload_model=args.offload_model, step_cache=args.step_cache_spec, **v2v)
+    if pipe.last_step_plan is not None:
+        logging.info('step cache: computed %d of %d steps: %s' % (sum(pipe.last_step_plan), len(pipe.last_step_plan),
+                                                                   ''.join('C' if c else 's' for c in pipe.last_step_plan)))
     if rank == 0:
         if args.save_file is None:
             args.save_file = default_save_name(args)

@@ -6,7 +6,9 @@ decode; this is the call itself on the wall clock, so that the product of the tw
 Random-init weights of the shipped architectures (no checkpoint / tokenizer files in the image): the tokenizer is replaced by a word hash with the reference's
 output contract (ids, mask of text_len 512); everything behind it is the product path.
 
-usage: python tools/e2e_video.py [--workload 1080p|720p] [--steps 50] [--solver unipc]      -> one JSON line on stdout
+usage: python tools/e2e_video.py [--workload 1080p|720p] [--steps 50] [--solver unipc] [--step_cache SPEC]      -> one JSON line on stdout
+--step_cache (opt-in step cache): a threshold (a number), or an explicit plan of C (compute) / S (skip) letters, repeated to
+--steps entries — `CS` = every other step.
 """
 import argparse
 import json
@@ -46,7 +48,15 @@ def main():
     ap.add_argument('--solver', default='unipc', choices=['unipc', 'dpm++'])
     ap.add_argument('--prompt-words', type=int, default=511)
     ap.add_argument('--neg-words', type=int, default=129)
+    ap.add_argument('--step_cache', default=None, help='threshold, or a plan of C / S letters repeated over the steps (CS = every other step)')
     args = ap.parse_args()
+    step_cache = None
+    if args.step_cache is not None:
+        pat = args.step_cache.upper()
+        if pat and set(pat) <= {'C', 'S'}:
+            step_cache = [pat[i % len(pat)] == 'C' for i in range(args.steps)]
+        else:
+            step_cache = float(args.step_cache)
     import wan
     import weights as Wt
     from wan.configs import WAN_CONFIGS
@@ -87,7 +97,7 @@ def main():
     t0 = time.perf_counter()
     start.record()
     video = pipe.generate(prompt, size=size, frame_num=81, sampling_steps=args.steps, sample_solver=args.solver, n_prompt=negative, seed=42,
-                          offload_model=True, callback=callback)
+                          offload_model=True, callback=callback, step_cache=step_cache)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     t1 = time.perf_counter()
@@ -98,9 +108,15 @@ def main():
     assert frames.dtype == torch.uint8 and tuple(frames.shape) == (81, size[1], size[0], 3)
     step_ms = [a.elapsed_time(b) for a, b in zip([start] + marks[:-1], marks)]
     mid = sorted(step_ms[1:])[len(step_ms[1:]) // 2] if len(step_ms) > 1 else step_ms[0]
+    plan = pipe.last_step_plan
+    med = lambda v: sorted(v)[len(v) // 2] if v else None      # noqa: E731
+    by_kind = {} if plan is None else {     # a step as the loop sees it: the forward(s) + CFG + the scheduler update (step 0 left out: prompt caches)
+        'median_computed_step_ms': med([m for m, c in list(zip(step_ms, plan))[1:] if c]),
+        'median_skipped_step_ms': med([m for m, c in list(zip(step_ms, plan))[1:] if not c])}
     line = {'what': 'WanT2V.generate end to end (tools/e2e_video.py): text encoder x 2 prompts + %d denoising steps (two guidance branches through WanModel.forward_pair, CFG 5.0, %s) '
                     '+ WanVAE.decode, offload_model=True (the reference default), one call on the wall clock' % (args.steps, args.solver),
-            'workload': '14B T2V %dx%dx81f' % size, 'sampling_steps': args.steps, 'sec_per_video_measured': wall,
+            'workload': '14B T2V %dx%dx81f' % size, 'sampling_steps': args.steps,
+            'step_cache': args.step_cache, **by_kind, 'steps_computed': sum(pipe.last_step_plan) if pipe.last_step_plan is not None else args.steps, 'sec_per_video_measured': wall,
             'first_step_ms_incl_text_encoder_and_prompt_caches': step_ms[0], 'median_later_step_ms': mid, 'sum_steps_s': sum(step_ms) / 1e3,
             'after_last_step_s_vae_decode_and_teardown': wall - sum(step_ms) / 1e3, 'uint8_frames_s_not_included': u8_s,
             'prompt_tokens': [args.prompt_words + 1, args.neg_words + 1], 'weights': 'random init (DiT seed 0, dim-96 WanVAE, umT5-XXL)', 'data': 'synthetic',
