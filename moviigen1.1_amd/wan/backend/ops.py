@@ -18,6 +18,11 @@ def _st():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _epilogue_dtype(epilogue):
+    """what a GEMM epilogue writes (MG_EPI_* in include/moviigen_hip.h): bf16 behind bias / bias+GELU, fp32 otherwise"""
+    return torch.bfloat16 if epilogue in (BIAS_BF16, BIAS_GELU_BF16) else torch.float32
+
+
 def _chk(t, dtype, name):
     if t is None:
         return
@@ -112,8 +117,7 @@ def gemm(a, w, bias, epilogue, out, gate=None):
     """out[M,N] (+)= a[M,K] @ w[N,K]^T (+bias ...) — see MG_EPI_* in include/moviigen_hip.h."""
     _chk(a, torch.bfloat16, 'a'); _chk(w, torch.bfloat16, 'w'); _chk(bias, torch.float32, 'bias')
     _chk(gate, torch.float32, 'gate')
-    want = torch.bfloat16 if epilogue in (BIAS_BF16, BIAS_GELU_BF16) else torch.float32
-    _chk(out, want, 'out')
+    _chk(out, _epilogue_dtype(epilogue), 'out')
     M, K = a.shape
     N = w.shape[0]
     if w.shape[1] != K or out.shape[0] != M or out.shape[1] != N:
@@ -146,8 +150,7 @@ def gemm_mxfp8(aq, a_scales, wq, w_scales, bias, epilogue, out, gate=None):
     of `gemm` (MG_EPI_* in include/moviigen_hip.h)."""
     _chk(aq, torch.uint8, 'aq'); _chk(a_scales, torch.uint8, 'a_scales'); _chk(wq, torch.uint8, 'wq')
     _chk(w_scales, torch.uint8, 'w_scales'); _chk(bias, torch.float32, 'bias'); _chk(gate, torch.float32, 'gate')
-    want = torch.bfloat16 if epilogue in (BIAS_BF16, BIAS_GELU_BF16) else torch.float32
-    _chk(out, want, 'out')
+    _chk(out, _epilogue_dtype(epilogue), 'out')
     M, K = aq.shape
     N = wq.shape[0]
     if (wq.shape[1] != K or out.shape[0] != M or out.shape[1] != N or tuple(a_scales.shape) != (M, K // 32)
@@ -207,23 +210,35 @@ def attention_workspace(device=None, stream=None):
     return ws
 
 
-def attention_hd128(q, kp, vp, out, lk, heads, scale, prescaled=False, reserve_cus=0, workspace='stream'):
+def attention_hd128(q, kp, vp, out, lk, heads, scale, prescaled=False, reserve_cus=0, workspace='stream', lse=None):
     """q [Lq, >=heads*128] bf16; kp/vp from pack_kv for the same lk keys; out [Lq, >=heads*128].
     prescaled: q was produced with rmsnorm_rope(out_scale=scale * ATTN_LOG2E) — `scale` is then only documentation.
     reserve_cus (prescaled entry): CUs the persistent grid leaves free for a kernel on another stream (the exchange).
-    workspace: 'stream' = attention_workspace() of the current stream; a uint8 tensor of the caller's; None = no tickets."""
+    workspace: 'stream' = attention_workspace() of the current stream; a uint8 tensor of the caller's; None = no tickets.
+    lse: fp32 [heads, Lq] that also receives the log-sum-exp of the scaled scores (ring attention), or None."""
     _chk(q, torch.bfloat16, 'q'); _chk(kp, torch.bfloat16, 'kp'); _chk(vp, torch.bfloat16, 'vp')
-    _chk(out, torch.bfloat16, 'out')
+    _chk(out, torch.bfloat16, 'out'); _chk(lse, torch.float32, 'lse')
     if min(kp.numel(), vp.numel()) < packed_kv_numel(int(lk), int(heads)):
         raise lib.MoviigenHipError('packed K/V buffers too small for lk keys')
+    if lse is not None and (lse.numel() < int(heads) * q.shape[0] or not lse.is_contiguous()):
+        raise lib.MoviigenHipError('lse must be a contiguous [heads, Lq] fp32 tensor')
     ws = attention_workspace(q.device) if isinstance(workspace, str) else workspace
+    head = (_p(q), q.stride(0), _p(kp), _p(vp), _p(out), out.stride(0))
     if prescaled:
-        lib.call('mg_attn_fwd_bf16_hd128_prescaled', _p(q), q.stride(0), _p(kp), _p(vp), _p(out), out.stride(0), None,
-                 q.shape[0], int(lk), int(heads), int(reserve_cus), _p(ws), _st())
+        lib.call('mg_attn_fwd_bf16_hd128_prescaled', *head, _p(lse), q.shape[0], int(lk), int(heads), int(reserve_cus), _p(ws), _st())
+    elif lse is not None:
+        lib.call('mg_attn_fwd_bf16_hd128_lse', *head, _p(lse), q.shape[0], int(lk), int(heads), float(scale), _p(ws), _st())
     else:
-        lib.call('mg_attn_fwd_bf16_hd128', _p(q), q.stride(0), _p(kp), _p(vp), _p(out), out.stride(0), q.shape[0],
-                 int(lk), int(heads), float(scale), _p(ws), _st())
+        lib.call('mg_attn_fwd_bf16_hd128', *head, q.shape[0], int(lk), int(heads), float(scale), _p(ws), _st())
     return out
+
+
+_attention_hd128 = attention_hd128      # the engine's own function, whatever a caller binds to the public name (bench.py times that one)
+
+
+def attention_hd128_lse(q, kp, vp, out, lse, lk, heads, scale, prescaled=False):
+    """attention_hd128(..., lse=lse) -> (out, lse)"""
+    return _attention_hd128(q, kp, vp, out, lk, heads, scale, prescaled=prescaled, lse=lse), lse
 
 
 def attention_generic(q, k, v, out, lk, heads, head_dim, scale):
@@ -594,24 +609,6 @@ def image_to_u8(image, lo=-1.0, hi=1.0):
     out = torch.empty(H, W, 3, dtype=torch.uint8, device=image.device)
     lib.call('mg_image_to_u8', _p(image), H, W, float(lo), float(hi), _p(out), _st())
     return out
-
-
-def attention_hd128_lse(q, kp, vp, out, lse, lk, heads, scale, prescaled=False):
-    """attention_hd128 that also writes lse [heads, Lq] fp32 (log-sum-exp of the scaled scores)."""
-    _chk(q, torch.bfloat16, 'q'); _chk(kp, torch.bfloat16, 'kp'); _chk(vp, torch.bfloat16, 'vp')
-    _chk(out, torch.bfloat16, 'out'); _chk(lse, torch.float32, 'lse')
-    if min(kp.numel(), vp.numel()) < packed_kv_numel(int(lk), int(heads)):
-        raise lib.MoviigenHipError('packed K/V buffers too small for lk keys')
-    if lse.numel() < int(heads) * q.shape[0] or not lse.is_contiguous():
-        raise lib.MoviigenHipError('lse must be a contiguous [heads, Lq] fp32 tensor')
-    ws = attention_workspace(q.device)
-    if prescaled:
-        lib.call('mg_attn_fwd_bf16_hd128_prescaled', _p(q), q.stride(0), _p(kp), _p(vp), _p(out), out.stride(0), _p(lse),
-                 q.shape[0], int(lk), int(heads), 0, _p(ws), _st())
-    else:
-        lib.call('mg_attn_fwd_bf16_hd128_lse', _p(q), q.stride(0), _p(kp), _p(vp), _p(out), out.stride(0), _p(lse),
-                 q.shape[0], int(lk), int(heads), float(scale), _p(ws), _st())
-    return out, lse
 
 
 def attention_merge(acc, lse_acc, part, lse_part, heads, first, out=None):

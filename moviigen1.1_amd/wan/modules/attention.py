@@ -18,6 +18,37 @@ from ..backend import ops
 __all__ = ['flash_attention', 'attention']
 
 
+def q_prescale(head_dim):
+    """factor folded into q when it is RMS-normed (ops.rmsnorm_rope out_scale) for attend(prescaled=True): the attention's
+    softmax_scale * log2(e) for the head_dim 128 kernel — q is rounded to bf16 once either way, and the kernel then needs
+    no per-score multiply (flash_attn applies softmax_scale to the fp32 scores: same product) — else 1."""
+    return ops.ATTN_LOG2E / math.sqrt(head_dim) if head_dim == 128 else 1.0
+
+
+def pack_tiles(k, v, klen, heads, tiles=None):
+    """the first `klen` rows of k, v [L, heads*128] bf16 (column views ok) as the 64-key tiles of the head_dim 128 kernel ->
+    (kp, vp); rows past klen are padding: never packed, never attended.  tiles: (kp, vp) buffers to fill, else new ones."""
+    if tiles is None:
+        n_pk = ops.packed_kv_numel(klen, heads)
+        tiles = tuple(torch.empty(n_pk, dtype=torch.bfloat16, device=k.device) for _ in range(2))
+    ops.pack_kv(k[:klen], v[:klen], heads, tiles[0], tiles[1])
+    return tiles
+
+
+def attend(q, k, v, out, klen, heads, head_dim, scale=None, prescaled=True, packed=False, tiles=None, reserve_cus=0):
+    """The engine's ONE attention launch: out [Lq, heads*head_dim] bf16 = softmax(scale * q k[:klen]^T) v[:klen] per head.
+    head_dim 128 runs the MFMA kernel on 64-key tiles — packed here (pack_tiles, into `tiles`), or k, v ARE tiles of klen
+    keys already (packed=True: the cross-attention K/V, packed once per prompt) — with q carrying q_prescale() unless
+    prescaled=False; any other head_dim runs the generic kernel on row-major k, v and an unscaled q."""
+    scale = 1.0 / math.sqrt(head_dim) if scale is None else scale
+    if head_dim != 128:
+        return ops.attention_generic(q, k, v, out, klen, heads, head_dim, scale)
+    if not packed:
+        k, v = pack_tiles(k, v, klen, heads, tiles)
+    # (the module attribute, looked up per call: bench.py and the tests time / count the launches by replacing it)
+    return ops.attention_hd128(q, k, v, out, klen, heads, scale, prescaled=prescaled, reserve_cus=reserve_cus)
+
+
 def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_scale=None, q_scale=None,
                     causal=False, window_size=(-1, -1), deterministic=False, dtype=torch.bfloat16, version=None):
     assert dtype == torch.bfloat16, 'the MI355X kernels are bf16'
@@ -39,14 +70,7 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
         ki = k[i, :kl].to(torch.bfloat16).reshape(kl, n * c).contiguous()
         vi = v[i, :kl].to(torch.bfloat16).reshape(kl, n * c).contiguous()
         oi = torch.empty(ql, n * c, dtype=torch.bfloat16, device=q.device)
-        if c == 128:
-            n_pk = ops.packed_kv_numel(kl, n)
-            kp = torch.empty(n_pk, dtype=torch.bfloat16, device=q.device)
-            vp = torch.empty(n_pk, dtype=torch.bfloat16, device=q.device)
-            ops.pack_kv(ki, vi, n, kp, vp)
-            ops.attention_hd128(qi, kp, vp, oi, kl, n, scale)
-        else:
-            ops.attention_generic(qi, ki, vi, oi, kl, n, c, scale)
+        attend(qi, ki, vi, oi, kl, n, c, scale=scale, prescaled=False)      # the one caller with an unscaled q
         out[i, :ql] = oi.view(ql, n, c)
     return out.type(out_dtype)
 

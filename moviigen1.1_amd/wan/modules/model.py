@@ -6,12 +6,15 @@ reference checkpoint layout: config.json + diffusion_pytorch_model*.safetensors)
 `forward(x, t, context, seq_len, clip_fea=None, y=None) -> List[Tensor[C,F,H,W] fp32]`.
 
 What differs is HOW a forward runs.  The reference composes ~40 torch ops per block under
-autocast; here a block is 14 kernel launches from libmoviigen_hip.so:
+autocast; here a block is 15 kernel launches from libmoviigen_hip.so at head_dim 128, 14 at any other:
 
-    ln_modulate -> gemm(QKV fused, N=3*dim) -> rmsnorm_rope(q, x softmax_scale*log2e) / rmsnorm_rope(k) / pack_kv
-    -> attention -> gemm(o) with `x += y*gate` fused  -> ln_modulate(norm3 affine) -> gemm(q)
-    -> rmsnorm -> attention(512 cached text keys) -> gemm(o) with `x += y` fused
-    -> ln_modulate -> gemm(ffn.0)+GELU fused -> gemm(ffn.2) with `x += y*gate` fused
+    self-attention    ln_modulate -> gemm(q|k|v fused, N=3*dim) -> rmsnorm_rope(q, x softmax_scale*log2e) -> rmsnorm_rope(k)
+                      -> pack_kv (head_dim 128 only: K/V as 64-key tiles) -> attention -> gemm(o) with `x += y*gate` fused
+    cross-attention   ln_modulate(norm3 affine) -> gemm(q) -> rmsnorm -> attention(512 cached text keys)
+                      -> gemm(o) with `x += y` fused
+    ffn               ln_modulate -> gemm(ffn.0)+GELU fused -> gemm(ffn.2) with `x += y*gate` fused
+
+(tests/test_gpu_parity.py::test_dit_forward_launch_sequence pins the whole forward's sequence.)
 
 The rounding points of the reference's autocast(bf16) execution are reproduced (SURVEY.md
 Appendix B): bf16 GEMM operands/results, fp32 accumulate, fp32 residual stream, fp32 norms and
@@ -22,6 +25,7 @@ K/V projections) is computed once per prompt and cached — identical values, 10
 
 There is no torch fallback: without the HIP library (or a GPU) forward() raises.
 """
+import collections
 import contextlib
 import json
 import math
@@ -32,6 +36,7 @@ import torch
 import torch.nn as nn
 
 from ..backend import ops
+from .attention import attend, pack_tiles, q_prescale
 from .attention import flash_attention      # operator seam (1): the reference binds it here by name (model.py:10)
 
 __all__ = ['WanModel']
@@ -91,51 +96,43 @@ class _Attn(nn.Module):
                                       'hybrid layouts call WanModel.forward (wan/distributed/ring.py)')
         d, N = self.dim, self.num_heads
         hd = d // N
-        scale = 1.0 / math.sqrt(hd)
         bf = torch.bfloat16
+        P = sp[1] if sp else 1
+        pos_rank = (sp[3] if len(sp) > 3 else sp[2]) if sp else 0
         outs = []
         for b in range(x.shape[0]):
             h = x[b].to(bf).contiguous()
             L, dev = h.shape[0], h.device
             grid = tuple(int(v) for v in grid_sizes[b].tolist())
-            rope = rope_cos_sin(hd, grid).to(dev)
-            q, k, v = (torch.empty(L, d, dtype=bf, device=dev) for _ in range(3))
+            q, k, v, qn, kn, a, o = (torch.empty(L, d, dtype=bf, device=dev) for _ in range(7))
             for lin, dst in ((self.q, q), (self.k, k), (self.v, v)):
                 ops.gemm(h, lin.weight, lin.bias, ops.BIAS_BF16, dst)
-            P = sp[1] if sp else 1
-            pos_rank = (sp[3] if len(sp) > 3 else sp[2]) if sp else 0
-            qn, kn = torch.empty_like(q), torch.empty_like(k)
-            # head_dim 128: softmax_scale * log2(e) folded into q before its one rounding to bf16, exactly as the fused
-            # layer loop does (WanModel._q_scale): the stand-alone operator and the fused one give the same bits
-            pre = hd == 128
-            ops.rmsnorm_rope(q, self.norm_q.weight, self.eps, hd, qn, rope, grid, pos_rank * L,
-                             out_scale=scale * ops.ATTN_LOG2E if pre else 1.0)
-            ops.rmsnorm_rope(k, self.norm_k.weight, self.eps, hd, kn, rope, grid, pos_rank * L)
-            a = torch.empty(L, d, dtype=bf, device=dev)
-
-            def attend(qg, kg, vg, ag, heads, klen):
-                if hd == 128:
-                    n_pk = ops.packed_kv_numel(klen, heads)
-                    kp, vp = torch.empty(n_pk, dtype=bf, device=dev), torch.empty(n_pk, dtype=bf, device=dev)
-                    ops.pack_kv(kg[:klen], vg[:klen], heads, kp, vp)
-                    ops.attention_hd128(qg, kp, vp, ag, klen, heads, scale, prescaled=pre)
-                else:
-                    ops.attention_generic(qg, kg, vg, ag, klen, heads, hd, scale)
+            # from here on the pieces of the fused layer loop (WanModel._self_attention): the same launches, the same bits
+            self.norm_rope_qk(q, k, qn, kn, rope_cos_sin(hd, grid).to(dev), grid, pos_rank * L)
             if P > 1:
-                from ..distributed.ulysses import HeadExchange
-                key = (sp[0], L, str(dev))
-                ex = self._xchg.get(key)
-                if ex is None:          # one live shape: the buffers and the stream are persistent, not per call
-                    self._xchg = {key: HeadExchange(sp[0], P, N, hd, L, dev)}
-                    ex = self._xchg[key]
-                ex.run(qn, kn, v, a, lambda qg, kg, vg, ag, n: attend(qg, kg, vg, ag, n, kg.shape[0]))
+                self._exchange(sp[0], P, L, dev).run(qn, kn, v, a, lambda qg, kg, vg, ag, n: attend(qg, kg, vg, ag, kg.shape[0], n, hd))
             else:
-                klen = min(L, int(seq_lens[b])) if seq_lens is not None else L
-                attend(qn, kn, v, a, N, klen)
-            o = torch.empty(L, d, dtype=bf, device=dev)
+                attend(qn, kn, v, a, min(L, int(seq_lens[b])) if seq_lens is not None else L, N, hd)
             ops.gemm(a, self.o.weight, self.o.bias, ops.BIAS_BF16, o)
             outs.append(o)
         return torch.stack(outs)
+
+    def norm_rope_qk(self, q, k, qn, kn, rope=None, grid=(1, 1, 1), pos0=0, prescale=True):
+        """RMS-norm + RoPE of the projected q and k [L, dim] bf16 (column views ok) -> qn, kn.  prescale: q_prescale() is folded into
+        qn before its one rounding to bf16, as attend() expects it; False for a caller-bound flash_attention, which scales itself.
+        k=None: q only (cross-attention: its k is normed once per prompt, WanModel._cross_kv)."""
+        hd = self.dim // self.num_heads
+        ops.rmsnorm_rope(q, self.norm_q.weight, self.eps, hd, qn, rope, grid, pos0, out_scale=q_prescale(hd) if prescale else 1.0)
+        if k is not None:
+            ops.rmsnorm_rope(k, self.norm_k.weight, self.eps, hd, kn, rope, grid, pos0)
+
+    def _exchange(self, group, P, L, dev):
+        """the HeadExchange of the stand-alone sequence-parallel operator: one live shape, its buffers and stream are persistent"""
+        from ..distributed.ulysses import HeadExchange
+        key = (group, L, str(dev))
+        if key not in self._xchg:
+            self._xchg = {key: HeadExchange(group, P, self.num_heads, self.dim // self.num_heads, L, dev)}
+        return self._xchg[key]
 
 
 class _Block(nn.Module):
@@ -212,6 +209,62 @@ MXFP8_SITES = {'wqkv': True, 'self_attn.o': False, 'cross_attn.q': False, 'cross
 MXFP8_FUSED_PRODUCERS = {'ln_modulate': False, 'gelu': False}
 GEMM_PRECISIONS = ('bf16', 'mxfp8')
 
+# one forward's shape and placement (WanModel._plan): fhw = the latent's (F, H, W); grid = its token grid; Lfull = the video's tokens,
+# which is also the valid key count of the self-attention (keys past it are padding); L, pos0 = this rank's rows of the (padded) sequence
+# and the position of its first one; n_valid = the video tokens among them (all of them unless padded); ws = the workspace of this
+# shape; rope = the (cos, sin) table of the grid; fa = _rebound_flash_attention() as this forward found it
+_Plan = collections.namedtuple('_Plan', 'fhw grid Lfull L pos0 n_valid ws rope fa')
+# block i's cross-attention K (RMS-normed) and V of one prompt.  layout 'fused': the operands of attend(packed=True) — 64-key tiles at
+# head_dim 128, row-major [text_len, dim] otherwise; 'seam': row-major whatever the head_dim, for a rebound flash_attention
+_CrossKV = collections.namedtuple('_CrossKV', 'k v layout')
+
+
+class _Linears:
+    """The six linears of ONE block and the LayerNorms in front of them, bound to what does not differ between their call sites: the
+    block's GEMM operands `lw`, its quantised weights `mx` ({site: (bytes, scales)} of the sites on fp8; None = bf16 mode), the
+    workspace and eps.  `feed` is the one place that decides which kernel quantises an fp8 site's operand."""
+    __slots__ = ('lw', 'mx', 'ws', 'eps', 'fuse')
+
+    def __init__(self, lw, mx, ws, eps, fuse):
+        self.lw, self.mx, self.ws, self.eps, self.fuse = lw, mx, ws, eps, fuse
+
+    def feed(self, site):
+        """how `site` gets its A operand: None = bf16, the site runs on mg_gemm_bf16 (also: site None, a reader outside the six);
+        'ln' / 'gelu' = the LayerNorm / ffn.0's GELU epilogue in front of it writes fp8 itself (the bf16 activation is NOT written);
+        'quant' = mg_quant_mxfp8_rows of the bf16 activation."""
+        if self.mx is None or site not in self.mx:
+            return None
+        if self.fuse and site in ('wqkv', 'cross_attn.q', 'ffn.0') and MXFP8_FUSED_PRODUCERS['ln_modulate']:
+            return 'ln'                         # (the three sites that are the only reader of a LayerNorm's output)
+        if self.fuse and site == 'ffn.2' and 'ffn.0' in self.mx and MXFP8_FUSED_PRODUCERS['gelu']:
+            return 'gelu'
+        return 'quant'
+
+    def _act(self, site):
+        """the quantised-activation buffers of `site`'s operand: h / a share one [L, dim] pair, u has its own"""
+        return (self.ws['uq'], self.ws['us']) if site == 'ffn.2' else (self.ws['hq'], self.ws['hs'])
+
+    def ln(self, site, x, scale, shift, add_one, round_norm_bf16=False):
+        """LayerNorm + modulate of the stream x in front of `site`: bf16 into ws['h'], or straight into the site's fp8 operand"""
+        if self.mx and self.feed(site) == 'ln':
+            ops.ln_modulate_mxfp8(x, scale, shift, add_one, self.eps, *self._act(site), round_norm_bf16=round_norm_bf16)
+        else:
+            ops.ln_modulate(x, scale, shift, add_one, self.eps, self.ws['h'], round_norm_bf16=round_norm_bf16)
+
+    def __call__(self, site, a, bias, epilogue, out, gate=None):
+        """out (+)= a @ W[site]^T with `epilogue` (ops.gemm).  On an fp8 site `a` is read only where feed() says 'quant'; ffn.0 in front
+        of a 'gelu'-fed ffn.2 writes that site's fp8 operand and not `out`."""
+        feed = self.feed(site) if self.mx else None             # (bf16 mode: not even the call, six times a block)
+        if feed is None:
+            return ops.gemm(a, self.lw[site], bias, epilogue, out, gate=gate)
+        aq, a_s = self._act(site)
+        if feed == 'quant':
+            ops.quant_mxfp8(a, aq, a_s)
+        wq, w_s = self.mx[site]
+        if site == 'ffn.0' and self.feed('ffn.2') == 'gelu':
+            return ops.gemm_mxfp8_gelu_q(aq, a_s, wq, w_s, bias, *self._act('ffn.2'))
+        return ops.gemm_mxfp8(aq, a_s, wq, w_s, bias, epilogue, out, gate=gate)
+
 
 class WanModel(nn.Module):
     ignore_for_config = ['patch_size', 'cross_attn_norm', 'qk_norm', 'text_dim', 'window_size']
@@ -255,7 +308,9 @@ class WanModel(nn.Module):
         # ranks, ring attention across the `ring_size` groups; None = derive from sp_size / ring
         self.uly_group, self.uly_size, self.ring_group, self.ring_size, self.ring_rank = None, None, None, None, 0
         self._packed = None
-        self.gemm_precision = 'bf16'    # set_gemm_precision: 'mxfp8' = the six per-block linears on the block-scaled MFMA (opt-in)
+        self._shards = None             # wan.distributed.fsdp.BlockShards installs itself here: the GEMM weights are block-sharded
+        self._freqs = None              # the reference's complex RoPE table, built by the `freqs` property
+        self.gemm_precision = 'bf16'   # set_gemm_precision: 'mxfp8' = the six per-block linears on the block-scaled MFMA (opt-in)
         self._mx = None                 # their quantised weights, built once per set of weights
         self._mx_fuse = True            # False: every fp8 site quantises its bf16 activation with mg_quant_mxfp8_rows (tests, tools/bench_gemm_mxfp8.py)
         self._ws = {}
@@ -270,7 +325,7 @@ class WanModel(nn.Module):
     def freqs(self):
         """the reference's complex RoPE table [1024, head_dim/2] (model.py:473-478), built on demand for callers of
         the operator seam; the engine's kernels use rope_cos_sin() instead."""
-        if getattr(self, '_freqs', None) is None:
+        if self._freqs is None:
             d = self.dim // self.num_heads
 
             def params(dim):
@@ -389,7 +444,7 @@ class WanModel(nn.Module):
                                'and has no CPU implementation')
         if self._lora:
             raise RuntimeError(f'adapters {self._lora} are merged into the weights already: unload_lora() first')
-        if getattr(self, '_shards', None) is not None:
+        if self._shards is not None:
             raise NotImplementedError('load_lora needs resident weights: merge before the weights are block-sharded '
                                       '(wan.distributed.fsdp shard_model; WanT2V(lora=...) does it in that order)')
         if isinstance(adapters, (str, os.PathLike, dict)):
@@ -442,7 +497,7 @@ class WanModel(nn.Module):
             raise RuntimeError('WanModel.forward needs the model on a HIP device (model.to("cuda")): the hot '
                                'path has no CPU implementation — use oracle/ for CPU reference numbers')
         pk = {'layers': []}
-        sharded = getattr(self, '_shards', None) is not None
+        sharded = self._shards is not None
         for b in self.blocks:
             sa, ca = b.self_attn, b.cross_attn
             lw = dict(bqkv=torch.cat([sa.q.bias, sa.k.bias, sa.v.bias]).contiguous(),
@@ -471,7 +526,7 @@ class WanModel(nn.Module):
         embeddings, the once-per-prompt cross k|v and the head are not touched."""
         if precision not in GEMM_PRECISIONS:
             raise ValueError(f'gemm precision must be one of {GEMM_PRECISIONS}, got {precision!r}')
-        if precision == 'mxfp8' and getattr(self, '_shards', None) is not None:
+        if precision == 'mxfp8' and self._shards is not None:
             raise NotImplementedError("set_gemm_precision('mxfp8') needs resident weights: block-sharded weights (wan.distributed.fsdp) "
                                       'are gathered in bf16 per block and are not quantised')
         if precision != self.gemm_precision:
@@ -504,7 +559,7 @@ class WanModel(nn.Module):
 
     def drop_step_cache(self):
         """free the step cache's buffers (xin, the residuals, the reduction scratch) and forget the stats"""
-        for ws in getattr(self, '_ws', {}).values():
+        for ws in self._ws.values():
             for k in ('xin', 'resid', 'resid_stats'):
                 ws.pop(k, None)
         self.step_cache_stats = {}
@@ -529,9 +584,7 @@ class WanModel(nn.Module):
         """(e [N, dim], e0 [N, 6 dim]) fp32 of the N timesteps by the forward's own kernels (reference model.py:541-545): what the
         step-cache plan is a function of (wan/utils/step_cache.py)."""
         dev, d = self.patch_embedding.weight.device, self.dim
-        tt = timesteps.reshape(-1).to(dev)
-        if tt.dtype not in (torch.int64, torch.float32, torch.float64):
-            tt = tt.to(torch.float32)
+        tt = self._timesteps(timesteps)
         n = tt.numel()
         f32 = dict(dtype=torch.float32, device=dev)
         sin, e1 = torch.empty(1, self.freq_dim, **f32), torch.empty(d, **f32)
@@ -539,6 +592,11 @@ class WanModel(nn.Module):
         for i in range(n):
             self._time_embedding(tt[i:i + 1], sin, e1, e[i], e0[i])
         return e, e0
+
+    def _timesteps(self, t):
+        """timesteps as a flat tensor on the model's device, of a dtype mg_sinusoid_embed reads (int64, fp32, fp64; any other -> fp32)"""
+        tt = t.reshape(-1).to(self.patch_embedding.weight.device)
+        return tt if tt.dtype in (torch.int64, torch.float32, torch.float64) else tt.to(torch.float32)
 
     def _time_embedding(self, tt, sin, e1, e, e0):
         ops.sinusoid_embed(tt, self.freq_dim, sin)
@@ -549,38 +607,18 @@ class WanModel(nn.Module):
 
     def _mx_layers(self):
         """per block {site: (e4m3 bytes [N, K], scale bytes [N, K/32])} for the sites MXFP8_SITES enables"""
-        if getattr(self, '_shards', None) is not None:
+        if self._shards is not None:
             raise NotImplementedError("gemm precision 'mxfp8' does not support block-sharded weights (wan.distributed.fsdp)")
         if self._mx is None:
             self._mx = [{site: ops.quant_mxfp8(lw[site]) for site, on in MXFP8_SITES.items() if on}
                         for lw in self._pack()['layers']]
         return self._mx
 
-    def _linear(self, site, a, act, lw, mx, bias, epilogue, out, gate=None, quantised=False):
-        """one of the six per-block linears: mg_gemm_bf16, or (mxfp8 mode, site enabled) quantise the activation into the
-        workspace and run mg_gemm_mxfp8.  `act` names the activation's quantised buffers in the workspace; quantised: its producer
-        has filled them already (`a` is then not read)."""
-        if mx is None or site not in mx:
-            return ops.gemm(a, lw[site], bias, epilogue, out, gate=gate)
-        aq, a_s = act
-        if not quantised:
-            ops.quant_mxfp8(a, aq, a_s)
-        return ops.gemm_mxfp8(aq, a_s, mx[site][0], mx[site][1], bias, epilogue, out, gate=gate)
-
-    def _ln(self, site, mx, act, x, scale, shift, add_one, h, round_norm_bf16=False):
-        """the LayerNorm + modulate in front of `site`, whose only consumer that site is: straight into the quantised buffers `act` when
-        the site runs on fp8 and the fused producer is wired in (True: h is NOT written), else bf16 into h (False)."""
-        if mx is not None and site in mx and self._mx_fuse and MXFP8_FUSED_PRODUCERS['ln_modulate']:
-            ops.ln_modulate_mxfp8(x, scale, shift, add_one, self.eps, act[0], act[1], round_norm_bf16=round_norm_bf16)
-            return True
-        ops.ln_modulate(x, scale, shift, add_one, self.eps, h, round_norm_bf16=round_norm_bf16)
-        return False
-
     def _layer(self, i):
         """GEMM operands of block i: resident, or (block-sharded mode, wan.distributed.fsdp) views of
         the all-gather buffer, with block i+1's gather already in flight on the comm stream."""
         lw = self._pack()['layers'][i]
-        sh = getattr(self, '_shards', None)
+        sh = self._shards
         if sh is None:
             return lw
         return {**lw, **sh.fetch(i)}
@@ -598,7 +636,6 @@ class WanModel(nn.Module):
             d, f = self.dim, self.ffn_dim
             bf, f32 = torch.bfloat16, torch.float32
             hd = d // self.num_heads
-            Ltot = L * self.sp_size
             e = lambda *s, dt=bf: torch.empty(*s, dtype=dt, device=dev)  # noqa: E731
             ws = dict(x=e(L, d, dt=f32), h=e(L, d), qkv=e(L, 3 * d), q=e(L, d), k=e(L, d), a=e(L, d),
                       u=e(L, f), tok=e(L, self.in_dim * math.prod(self.patch_size)),
@@ -641,7 +678,7 @@ class WanModel(nn.Module):
     # 168-170) — independent of t, so done once per prompt tensor and cached
     # ------------------------------------------------------------------------------------------
     def _context(self, ctx):
-        """-> (ctx, emb [text_len, dim] bf16, layers): `layers[i]` is block i's cross-attention (K, V) — filled by
+        """-> (ctx, emb [text_len, dim] bf16, layers): `layers[i]` is block i's cross-attention _CrossKV — filled by
         _cross_kv the first time block i runs for this prompt, i.e. while that block's weights are at hand anyway
         (block-sharded mode: no extra all-gather sweep over the 28 GB of weights per new prompt)."""
         key = self._ctx_key(ctx)
@@ -663,88 +700,101 @@ class WanModel(nn.Module):
         self._ctx_cache[key] = (ctx, emb, [None] * self.num_layers)  # keep ctx alive so data_ptr stays unique
         return self._ctx_cache[key]
 
-    def _cross_kv(self, i, lw, emb, row_major=False):
-        """cross-attention K (RMS-normed) and V of block i for one prompt (reference model.py:168-170): packed tile
-        buffers for the head_dim 128 kernel, row-major [text_len, dim] otherwise (and for a rebound flash_attention)."""
+    def _cross_kv(self, i, lw, emb, layout):
+        """cross-attention K (RMS-normed) and V of block i for one prompt (reference model.py:168-170) -> _CrossKV in `layout`"""
         dev, d, hd = emb.device, self.dim, self.dim // self.num_heads
         Lc, bf = self.text_len, torch.bfloat16
         kv = torch.empty(Lc, 2 * d, dtype=bf, device=dev)
         ops.gemm(emb, lw['wkv_c'], lw['bkv_c'], ops.BIAS_BF16, kv)
         kc = torch.empty(Lc, d, dtype=bf, device=dev)
         ops.rmsnorm_rope(kv[:, :d], self.blocks[i].cross_attn.norm_k.weight, self.eps, hd, kc)
-        if hd == 128 and not row_major:
-            n_pk = ops.packed_kv_numel(Lc, self.num_heads)
-            kcp, vcp = torch.empty(n_pk, dtype=bf, device=dev), torch.empty(n_pk, dtype=bf, device=dev)
-            ops.pack_kv(kc, kv[:, d:], self.num_heads, kcp, vcp)
-            return kcp, vcp
-        return kc, kv[:, d:].clone()
+        if hd == 128 and layout == 'fused':
+            return _CrossKV(*pack_tiles(kc, kv[:, d:], Lc, self.num_heads), layout)
+        return _CrossKV(kc, kv[:, d:].clone(), layout)
 
-    # ------------------------------------------------------------------------------------------
-    def _q_scale(self):
-        """factor the fused forward folds into q when it is RMS-normed (ops.rmsnorm_rope out_scale): the attention's
-        softmax_scale * log2(e) for the head_dim 128 kernel — q is rounded to bf16 once either way, and the kernel then
-        needs no per-score multiply (flash_attn applies softmax_scale to the fp32 scores: same product) — else 1."""
-        hd = self.dim // self.num_heads
-        return ops.ATTN_LOG2E / math.sqrt(hd) if hd == 128 else 1.0
-
-    def _attention(self, q, k, v, out, lk, heads):
-        """head_dim 128: q PRE-SCALED (_q_scale), k, v PACKED tile buffers (ops.pack_kv); otherwise row-major."""
-        hd = self.dim // self.num_heads
-        scale = 1.0 / math.sqrt(hd)
-        if hd == 128:
-            ops.attention_hd128(q, k, v, out, lk, heads, scale, prescaled=True)
-        else:
-            ops.attention_generic(q, k, v, out, lk, heads, hd, scale)
-
-    def _self_attention(self, ws, blk, grid, rope, L, pos0):
-        """model.py:127-156 (and the Ulysses variant xdit_context_parallel.py:155-198)."""
+    # the three parts of a block (reference model.py:297-311); `lin` is the block's _Linears, m its six modulation rows
+    def _self_attention(self, plan, blk):
+        """ws['qkv'] -> ws['a']: reference model.py:127-156 (and the Ulysses variant xdit_context_parallel.py:155-198)."""
         d, hd, N = self.dim, self.dim // self.num_heads, self.num_heads
+        ws, L = plan.ws, plan.L
         qkv = ws['qkv']
-        sa = blk.self_attn
-        fa = _rebound_flash_attention() if self.sp_size == 1 and not self.sp_force else None
-        ops.rmsnorm_rope(qkv[:, :d], sa.norm_q.weight, self.eps, hd, ws['q'], rope, grid, pos0,
-                         out_scale=self._q_scale() if fa is None else 1.0)
-        ops.rmsnorm_rope(qkv[:, d:2 * d], sa.norm_k.weight, self.eps, hd, ws['k'], rope, grid, pos0)
+        q, k, v, a = ws['q'], ws['k'], qkv[:, 2 * d:], ws['a']
+        fa = plan.fa if self.sp_size == 1 and not self.sp_force else None
+        blk.self_attn.norm_rope_qk(qkv[:, :d], qkv[:, d:2 * d], q, k, plan.rope, plan.grid, plan.pos0, prescale=fa is None)
         if fa is not None:
             # operator seam (1): the caller's function gets the reference's call (model.py:146-151): q, k roped
             # [1, L, N, hd] (UNSCALED: softmax_scale is the callee's business), v, k_lens, window_size
-            y = fa(q=ws['q'].view(1, L, N, hd), k=ws['k'].view(1, L, N, hd), v=qkv[:, 2 * d:].reshape(1, L, N, hd),
-                   k_lens=torch.tensor([self._kv_valid]), window_size=self.window_size)
-            ws['a'].copy_(y.reshape(L, d))
-            return
-        if self.sp_size == 1 and not self.sp_force:
-            if hd == 128:
-                kv = self._kv_valid        # rows past the video's tokens are padding: never packed, never attended
-                ops.pack_kv(ws['k'][:kv], qkv[:kv, 2 * d:], N, ws['kp'], ws['vp'])
-                self._attention(ws['q'], ws['kp'], ws['vp'], ws['a'], kv, N)
-            else:
-                self._attention(ws['q'], ws['k'], qkv[:, 2 * d:], ws['a'], self._kv_valid, N)
+            y = fa(q=q.view(1, L, N, hd), k=k.view(1, L, N, hd), v=v.reshape(1, L, N, hd),
+                   k_lens=torch.tensor([plan.Lfull]), window_size=self.window_size)
+            a.copy_(y.reshape(L, d))
             return
         U, R = self._sp_layout()
-        rg = self.ring_group if self.ring_group is not None else self.sp_group
-        rr = self.ring_rank if self.uly_size is not None else self.sp_rank
-        scale = 1.0 / math.sqrt(hd)
-        q, k, v, a = ws['q'], ws['k'], qkv[:, 2 * d:], ws['a']
+        tiles = (ws['kp'], ws['vp']) if 'kp' in ws else None
+        # while an exchange is in flight the persistent attention grid leaves `reserve_cus` CUs to RCCL's kernels
+        reserve = ws['xchg'].reserve_cus if 'xchg' in ws else 0
 
-        def attend(qg, kg, vg, ag, heads):      # operands may be strided column views; ag contiguous
+        def attn(qg, kg, vg, ag, heads):        # operands may be strided column views; ag contiguous
             if R > 1:                           # ring attention across the groups (hd 128 only)
                 from ..distributed.ring import ring_attention
-                ring_attention(qg, kg, vg, ag, ws, rg, R, rr, heads, scale, prescaled=True)
-            elif hd == 128:
-                kv = min(kg.shape[0], self._kv_valid)       # keys past the video's tokens are padding (k_lens)
-                ops.pack_kv(kg[:kv], vg[:kv], heads, ws['kp'], ws['vp'])
-                # while an exchange is in flight the persistent attention grid leaves `reserve_cus` CUs to RCCL's kernels
-                ops.attention_hd128(qg, ws['kp'], ws['vp'], ag, kv, heads, scale, prescaled=True,
-                                    reserve_cus=ws['xchg'].reserve_cus if 'xchg' in ws else 0)
-            else:
-                ops.attention_generic(qg, kg, vg, ag, min(kg.shape[0], self._kv_valid), heads, hd, scale)
+                rg = self.ring_group if self.ring_group is not None else self.sp_group
+                rr = self.ring_rank if self.uly_size is not None else self.sp_rank
+                ring_attention(qg, kg, vg, ag, ws, rg, R, rr, heads, 1.0 / math.sqrt(hd), prescaled=True)
+            else:                               # keys past the video's tokens are padding (k_lens)
+                attend(qg, kg, vg, ag, min(kg.shape[0], plan.Lfull), heads, hd, tiles=tiles, reserve_cus=reserve)
 
         if U > 1 or self.sp_force:
             # Ulysses: packed q|k|v exchange per head group on the comm stream, pipelined against the attention
             # launches (xdit_context_parallel.py:185-190 / model_seq.py:232-256)
-            ws['xchg'].run(q, k, v, a, attend)
-        else:                                   # pure ring: every rank keeps all heads
-            attend(q, k, v, a, N)
+            ws['xchg'].run(q, k, v, a, attn)
+        else:                                   # single GPU, or pure ring: every rank keeps all heads
+            attn(q, k, v, a, N)
+
+    def _block_self_attn(self, i, blk, plan, lin, m, share):
+        """x += gate * self_attn(modulated LN(x)).  Block 0 is where forward_pair shares: 'save' keeps the stream as it stands
+        behind this part (ws['x0']), 'reuse' takes that copy instead of computing it."""
+        ws, x = plan.ws, plan.ws['x']
+        if i == 0 and share == 'reuse':
+            assert 'x0' in ws, "share='reuse' follows a share='save' forward of the same latent and t"
+            x.copy_(ws['x0'])                   # block 0 up to here saw the latent and t only: the 'save' forward's stream, bit for bit
+            return
+        custom = _replaced_forward(blk.self_attn)
+        if custom is None:
+            lin.ln('wqkv', x, m[1], m[0], True, round_norm_bf16=(i == 0))
+            lin('wqkv', ws['h'], lin.lw['bqkv'], ops.BIAS_BF16, ws['qkv'])
+            self._self_attention(plan, blk)
+            lin('self_attn.o', ws['a'], blk.self_attn.o.bias, ops.GATE_RESID_F32, x, gate=m[2])
+        else:
+            # operator seam (2) of the reference (text2video.py:97-100): the caller replaced
+            # block.self_attn.forward — call it with the reference's arguments (the bf16 h) and keep the fused rest
+            lin.ln(None, x, m[1], m[0], True, round_norm_bf16=(i == 0))
+            y = custom(ws['h'][None], torch.tensor([plan.Lfull]), torch.tensor([list(plan.grid)]), self.freqs)
+            ops.gate_residual(x, y[0].to(torch.bfloat16).contiguous(), m[2])
+        if i == 0 and share == 'save':
+            if 'x0' not in ws:
+                ws['x0'] = torch.empty_like(x)
+            ws['x0'].copy_(x)
+
+    def _block_cross_attn(self, i, blk, plan, lin, ctx_emb, ctx_layers):
+        """x += cross_attn(norm3(x), text): the text keys / values are made the first time block i meets this prompt"""
+        ws, x, ca = plan.ws, plan.ws['x'], blk.cross_attn
+        N, hd, fa = self.num_heads, self.dim // self.num_heads, plan.fa
+        layout = 'fused' if fa is None else 'seam'
+        if ctx_layers[i] is None or ctx_layers[i].layout != layout:
+            ctx_layers[i] = self._cross_kv(i, lin.lw, ctx_emb, layout)
+        kc, vc, _ = ctx_layers[i]
+        lin.ln('cross_attn.q', x, blk.norm3.weight, blk.norm3.bias, False)
+        lin('cross_attn.q', ws['h'], ca.q.bias, ops.BIAS_BF16, ws['q'])
+        ca.norm_rope_qk(ws['q'], None, ws['k'], None, prescale=fa is None)
+        if fa is not None:
+            # operator seam (1), reference model.py:176: flash_attention(q, k, v, k_lens=context_lens) with
+            # context_lens = None for T2V
+            y = fa(ws['k'].view(1, plan.L, N, hd), kc.view(1, -1, N, hd), vc.reshape(1, -1, N, hd), k_lens=None)
+            ws['a'].copy_(y.reshape(plan.L, self.dim))
+        elif self.cross_attn_head_sharded and self.sp_size > 1:
+            self._cross_attention_head_sharded(ws, kc, vc)
+        else:
+            attend(ws['k'], kc, vc, ws['a'], self.text_len, N, hd, packed=True)
+        lin('cross_attn.o', ws['a'], ca.o.bias, ops.GATE_RESID_F32, x)
 
     def _cross_attention_head_sharded(self, ws, kc, vc):
         """model_seq.py:271-294: q through the seq->head all-to-all, K/V narrowed to this rank's heads (shrink_head),
@@ -763,16 +813,12 @@ class WanModel(nn.Module):
             ks, vs = kc[ur * nl * per_head:(ur + 1) * nl * per_head], vc[ur * nl * per_head:(ur + 1) * nl * per_head]
         else:
             ks, vs = kc[:, ur * nl * hd:(ur + 1) * nl * hd], vc[:, ur * nl * hd:(ur + 1) * nl * hd]
-        self._attention(qg, ks, vs, ag, self.text_len, nl)
+        attend(qg, ks, vs, ag, self.text_len, nl, hd, packed=True)
         ulysses.head_to_seq(ag, ws['a'], ug, U, N, hd)
 
-    @torch.no_grad()
-    def _forward_one(self, lat, t, ctx, seq_len, share=None):
-        """share: None, or the two halves of forward_pair — 'save' keeps the residual stream as it stands behind block 0's self-attention
-        (ws['x0']), 'reuse' starts from that copy instead of recomputing it (same latent, same t: nothing before that point reads `ctx`)."""
-        pk = self._pack()
-        dev = lat.device
-        lat = lat.to(torch.float32).contiguous()
+    # one forward: plan -> embed -> [step cache: open, skip exit] -> blocks -> [step cache: capture] -> head
+    def _plan(self, lat, seq_len):
+        """shape and placement of one forward (-> _Plan): what every later stage is told instead of working it out again"""
         C, F, H, W = lat.shape
         pt, ph, pw = self.patch_size
         assert pt == 1, 'temporal patch size 1 (reference config)'
@@ -793,133 +839,94 @@ class WanModel(nn.Module):
                 'sequence parallel needs L % sp == 0, heads % sp == 0 and no padding'
         L = Ltot // P
         pos0 = self.sp_rank * L
-        n_valid = min(max(Lfull - pos0, 0), L)          # video tokens among this rank's rows (all of them unless padded)
-        self._kv_valid = Lfull
-        d, eps = self.dim, self.eps
-        ws = self._workspace(L, dev)
-        x = ws['x']
+        n_valid = min(max(Lfull - pos0, 0), L)
+        return _Plan((F, H, W), grid, Lfull, L, pos0, n_valid, self._workspace(L, lat.device), self._rope_tab(grid, lat.device),
+                     _rebound_flash_attention())
 
-        reuse = share == 'reuse'
-        step, step_stats = self._step_mode or (None, False)
-        resid = None
-        if step == 'skip':
+    def _embed(self, plan, lat, t, patches=True):
+        """patch embedding (reference model.py:529-531) of this rank's rows into the residual stream ws['x']: bf16 result, fp32 storage
+        (patches=False: forward_pair brings x back whole); then the time embedding (:541-545, fp32) and the head's modulation rows"""
+        ws, x, n_valid = plan.ws, plan.ws['x'], plan.n_valid
+        if patches:
+            _, ph, pw = self.patch_size
+            if self.sp_size == 1:
+                ops.patchify(lat, ph, pw, ws['tok'])
+            else:
+                full = torch.empty(plan.Lfull, ws['tok'].shape[1], dtype=torch.bfloat16, device=lat.device)
+                ops.patchify(lat, ph, pw, full)
+                ws['tok'][:n_valid].copy_(full[plan.pos0:plan.pos0 + n_valid])  # torch.chunk(x, P, dim=1)[rank]
+            if n_valid:
+                ops.gemm(ws['tok'][:n_valid], self._packed['patch_w'], self.patch_embedding.bias, ops.BIAS_F32, x[:n_valid])
+            if n_valid < plan.L:
+                x[n_valid:].zero_()                      # rows padded AFTER the patch embedding (no bias), :704-706
+        self._time_embedding(self._timesteps(t), ws['sin'], ws['e1'], ws['e'], ws['e0'])
+        ops.add_rows(self.head.modulation.data.reshape(2, self.dim), ws['e'].reshape(1, self.dim), ws['hmod'], 1)
+
+    def _step_open(self, ws, ctx, reuse):
+        """step cache 1/3, behind the embedding -> the residual buffer of (this workspace, ctx).
+        'compute' keeps the embedded stream in ws['xin'] ('reuse': the 'save' half's copy — the same latent, the same data)."""
+        if self._step_mode[0] == 'skip':
             # 'reuse' finds x as the 'save' half embedded it: a skipped forward reads the stream and never writes it
             resid = self._step_resid(ws, ctx, create=False)
             if resid is None:
                 raise RuntimeError("step_cache('skip'): no residual for this sequence length and context — a step_cache('compute') forward "
                                    'of the same context has to come first (weight changes and drop_step_cache() drop the residuals)')
-        else:
-            if share == 'save' and 'x0' not in ws:
-                ws['x0'] = torch.empty_like(x)
-            assert not reuse or 'x0' in ws, "share='reuse' follows a share='save' forward of the same latent and t"
-        if step == 'compute':
-            if 'xin' not in ws:
-                assert not reuse, "share='reuse' follows a share='save' forward in the same step_cache scope"
-                ws['xin'] = torch.empty_like(x)
-            resid = self._step_resid(ws, ctx, create=True)
+            return resid
+        if 'xin' not in ws:
+            assert not reuse, "share='reuse' follows a share='save' forward in the same step_cache scope"
+            ws['xin'] = torch.empty_like(ws['x'])
+        if not reuse:
+            ws['xin'].copy_(ws['x'])
+        return self._step_resid(ws, ctx, create=True)
 
-        # patch embedding (model.py:529-531): bf16 result, residual stream kept in fp32 storage
-        if reuse:
-            pass                                         # x comes back whole behind block 0's self-attention
-        elif P == 1:
-            ops.patchify(lat, ph, pw, ws['tok'])
-        else:
-            full = torch.empty(Lfull, ws['tok'].shape[1], dtype=torch.bfloat16, device=dev)
-            ops.patchify(lat, ph, pw, full)
-            ws['tok'][:n_valid].copy_(full[pos0:pos0 + n_valid])  # torch.chunk(x, P, dim=1)[rank]
-        if n_valid and not reuse:
-            ops.gemm(ws['tok'][:n_valid], pk['patch_w'], self.patch_embedding.bias, ops.BIAS_F32, x[:n_valid])
-        if n_valid < L and not reuse:
-            x[n_valid:].zero_()                          # rows padded AFTER the patch embedding (no bias), :704-706
-        if step == 'compute' and not reuse:
-            ws['xin'].copy_(x)                           # ('reuse': the 'save' half's copy — the same latent, the same data)
+    def _step_capture(self, ws, ctx, resid):
+        """step cache 3/3, behind the last block: resid <- x - xin, what the blocks added to the stream, for the skipped steps that follow"""
+        if not self._step_mode[1]:
+            return ops.step_resid_capture(resid, ws['x'], ws['xin'])
+        if 'resid_stats' not in ws:
+            ws['resid_stats'] = (torch.empty(2, dtype=torch.float64, device=resid.device), ops.step_resid_partials(resid.device))
+        st, part = ws['resid_stats']
+        ops.step_resid_capture(resid, ws['x'], ws['xin'], st, part)
+        self.step_cache_stats[self._ctx_key(ctx)] = tuple(st.tolist())
 
-        # time embedding (model.py:541-545), fp32
-        tt = t.reshape(1).to(dev)
-        if tt.dtype not in (torch.int64, torch.float32, torch.float64):
-            tt = tt.to(torch.float32)
-        self._time_embedding(tt, ws['sin'], ws['e1'], ws['e'], ws['e0'])
-        ops.add_rows(self.head.modulation.data.reshape(2, d), ws['e'].reshape(1, d), ws['hmod'], 1)
-        if step == 'skip':
-            # no block runs: the residual the blocks added at this context's last computed step is added again, inside the head's LayerNorm
-            ops.resid_ln_modulate(x, resid, ws['hmod'][1], ws['hmod'][0], eps, ws['hf'])
-            return self._head_out(ws, grid, (F, H, W), dev)
+    def _block(self, i, blk, plan, mx, ctx_emb, ctx_layers, share):
+        """block i on the residual stream ws['x'] (reference model.py:297-311); mx: its quantised weights, None in bf16 mode"""
+        lin = _Linears(self._layer(i), mx, plan.ws, self.eps, self._mx_fuse)
+        m = plan.ws['mod'][6 * i:6 * i + 6]
+        self._block_self_attn(i, blk, plan, lin, m, share)
+        self._block_cross_attn(i, blk, plan, lin, ctx_emb, ctx_layers)
+        ws = plan.ws                            # ffn: x += gate * ffn.2(GELU(ffn.0(modulated LN(x))))
+        lin.ln('ffn.0', ws['x'], m[4], m[3], True)
+        lin('ffn.0', ws['h'], blk.ffn['0'].bias, ops.BIAS_GELU_BF16, ws['u'])
+        lin('ffn.2', ws['u'], blk.ffn['2'].bias, ops.GATE_RESID_F32, ws['x'], gate=m[5])
+
+    @torch.no_grad()
+    def _forward_one(self, lat, t, ctx, seq_len, share=None):
+        """share: None, or the two halves of forward_pair — 'save' keeps the residual stream as it stands behind block 0's self-attention
+        (ws['x0']), 'reuse' starts from that copy instead of recomputing it (same latent, same t: nothing before that point reads `ctx`)."""
+        pk = self._pack()
+        lat = lat.to(torch.float32).contiguous()
+        plan = self._plan(lat, seq_len)
+        ws, x = plan.ws, plan.ws['x']
+        self._embed(plan, lat, t, patches=share != 'reuse')       # ('reuse': x comes back whole behind block 0's self-attention)
+        resid = self._step_open(ws, ctx, share == 'reuse') if self._step_mode else None
+        if resid is not None and self._step_mode[0] == 'skip':
+            # step cache 2/3, the skip exit: no block runs — the residual the blocks added at this context's last computed step is added
+            # again, inside the head's LayerNorm
+            ops.resid_ln_modulate(x, resid, ws['hmod'][1], ws['hmod'][0], self.eps, ws['hf'])
+            return self._head_out(ws, plan.grid, plan.fhw, lat.device)
+
         ops.add_rows(pk['modulation'], ws['e0'], ws['mod'], 6)                       # model.py:292-295
-
         _, ctx_emb, ctx_layers = self._context(ctx)
-        rope = self._rope_tab(grid, dev)
-        mod = ws['mod']
-
         mxl = self._mx_layers() if self.gemm_precision == 'mxfp8' else None
-        qd, qf = (ws.get('hq'), ws.get('hs')), (ws.get('uq'), ws.get('us'))      # quantised [L, dim] / [L, ffn_dim] activation
         for i, blk in enumerate(self.blocks):
-            lw = self._layer(i)
-            mx = mxl[i] if mxl is not None else None
-            m = mod[6 * i:6 * i + 6]
-            # self attention
-            if i == 0 and reuse:
-                x.copy_(ws['x0'])                        # block 0 up to here saw the latent and t only: the 'save' forward's stream, bit for bit
-            else:
-                custom = _replaced_forward(blk.self_attn)
-                if custom is None:
-                    hq = self._ln('wqkv', mx, qd, x, m[1], m[0], True, ws['h'], round_norm_bf16=(i == 0))
-                    self._linear('wqkv', ws['h'], qd, lw, mx, lw['bqkv'], ops.BIAS_BF16, ws['qkv'], quantised=hq)
-                    self._self_attention(ws, blk, grid, rope, L, pos0)
-                    self._linear('self_attn.o', ws['a'], qd, lw, mx, blk.self_attn.o.bias, ops.GATE_RESID_F32, x, gate=m[2])
-                else:
-                    # operator seam (2) of the reference (text2video.py:97-100): the caller replaced
-                    # block.self_attn.forward — call it with the reference's arguments (the bf16 h) and keep the fused rest
-                    ops.ln_modulate(x, m[1], m[0], True, eps, ws['h'], round_norm_bf16=(i == 0))
-                    y = custom(ws['h'][None], torch.tensor([Lfull]), torch.tensor([list(grid)]), self.freqs)
-                    ops.gate_residual(x, y[0].to(torch.bfloat16).contiguous(), m[2])
-                if i == 0 and share == 'save':
-                    ws['x0'].copy_(x)
-            # cross attention (text keys/values cached per prompt)
-            ca = blk.cross_attn
-            fa = _rebound_flash_attention()
-            if ctx_layers[i] is None or (len(ctx_layers[i]) == 3) != (fa is not None):  # first forward with this prompt
-                ctx_layers[i] = self._cross_kv(i, lw, ctx_emb) if fa is None else \
-                    self._cross_kv(i, lw, ctx_emb, row_major=True) + ('row-major',)
-            kc, vc = ctx_layers[i][:2]
-            hq = self._ln('cross_attn.q', mx, qd, x, blk.norm3.weight, blk.norm3.bias, False, ws['h'])
-            self._linear('cross_attn.q', ws['h'], qd, lw, mx, ca.q.bias, ops.BIAS_BF16, ws['q'], quantised=hq)
-            ops.rmsnorm_rope(ws['q'], ca.norm_q.weight, eps, d // self.num_heads, ws['k'],
-                             out_scale=self._q_scale() if fa is None else 1.0)
-            if fa is not None:
-                # operator seam (1), reference model.py:176: flash_attention(q, k, v, k_lens=context_lens) with
-                # context_lens = None for T2V
-                N, hd = self.num_heads, d // self.num_heads
-                y = fa(ws['k'].view(1, L, N, hd), kc.view(1, -1, N, hd), vc.reshape(1, -1, N, hd), k_lens=None)
-                ws['a'].copy_(y.reshape(L, d))
-            elif self.cross_attn_head_sharded and P > 1:
-                self._cross_attention_head_sharded(ws, kc, vc)
-            else:
-                self._attention(ws['k'], kc, vc, ws['a'], self.text_len, self.num_heads)
-            self._linear('cross_attn.o', ws['a'], qd, lw, mx, ca.o.bias, ops.GATE_RESID_F32, x, gate=None)
-            # ffn
-            hq = self._ln('ffn.0', mx, qd, x, m[4], m[3], True, ws['h'])
-            uq = mx is not None and 'ffn.0' in mx and 'ffn.2' in mx and self._mx_fuse and MXFP8_FUSED_PRODUCERS['gelu']
-            if uq:       # ffn.0's GELU epilogue writes ffn.2's operand: ws['u'] is not written
-                if not hq:
-                    ops.quant_mxfp8(ws['h'], *qd)
-                ops.gemm_mxfp8_gelu_q(qd[0], qd[1], mx['ffn.0'][0], mx['ffn.0'][1], blk.ffn['0'].bias, qf[0], qf[1])
-            else:
-                self._linear('ffn.0', ws['h'], qd, lw, mx, blk.ffn['0'].bias, ops.BIAS_GELU_BF16, ws['u'], quantised=hq)
-            self._linear('ffn.2', ws['u'], qf, lw, mx, blk.ffn['2'].bias, ops.GATE_RESID_F32, x, gate=m[5], quantised=uq)
-
-        if step == 'compute':                            # what the blocks added to the stream, for the skipped steps that follow
-            if step_stats:
-                if 'resid_stats' not in ws:
-                    ws['resid_stats'] = (torch.empty(2, dtype=torch.float64, device=dev), ops.step_resid_partials(dev))
-                st, part = ws['resid_stats']
-                ops.step_resid_capture(resid, x, ws['xin'], st, part)
-                self.step_cache_stats[self._ctx_key(ctx)] = tuple(st.tolist())
-            else:
-                ops.step_resid_capture(resid, x, ws['xin'])
+            self._block(i, blk, plan, mxl[i] if mxl is not None else None, ctx_emb, ctx_layers, share)
+        if resid is not None:
+            self._step_capture(ws, ctx, resid)
 
         # head (model.py:333-343): fp32 end to end
-        ops.ln_modulate(x, ws['hmod'][1], ws['hmod'][0], True, eps, ws['hf'])
-        return self._head_out(ws, grid, (F, H, W), dev)
+        ops.ln_modulate(x, ws['hmod'][1], ws['hmod'][0], True, self.eps, ws['hf'])
+        return self._head_out(ws, plan.grid, plan.fhw, lat.device)
 
     def _head_out(self, ws, grid, fhw, dev):
         """head Linear on ws['hf'], the SP all-gather and unpatchify (model.py:342, :561-565)"""
@@ -933,18 +940,18 @@ class WanModel(nn.Module):
         ops.unpatchify(y, self.out_dim, grid[0], grid[1], grid[2], self.patch_size[1], self.patch_size[2], out)
         return out
 
+    def _retry_without_peer_copies(self, run):
+        """run() = the forward(s) of one call.  If a copy of the copy-engine transport was refused on some rank meanwhile (every rank
+        reads the same answer), the whole group goes back to the all-to-all collective, for good, and run() is repeated on it."""
+        out = run()
+        return run() if self._peer_transport_failed() else out
+
     def forward(self, x, t, context, seq_len, clip_fea=None, y=None):
         if clip_fea is not None or y is not None:
             raise NotImplementedError('image conditioning (i2v) is not part of MoviiGen1.1 T2V')
         t = t.reshape(-1)
-        outs = [self._forward_one(u, t[i if t.numel() > 1 else 0], c, seq_len)
-                for i, (u, c) in enumerate(zip(x, context))]
-        if self._peer_transport_failed():
-            # a copy of the copy-engine transport was refused on some rank during this forward (every rank reads the same answer): the
-            # whole group goes back to the all-to-all collective, for good, and the forward is repeated on it
-            outs = [self._forward_one(u, t[i if t.numel() > 1 else 0], c, seq_len)
-                    for i, (u, c) in enumerate(zip(x, context))]
-        return outs
+        return self._retry_without_peer_copies(lambda: [self._forward_one(u, t[i if t.numel() > 1 else 0], c, seq_len)
+                                                        for i, (u, c) in enumerate(zip(x, context))])
 
     def forward_pair(self, x, t, context, context_null, seq_len):
         """The two guidance branches of ONE denoising step (reference text2video.py:237-240: two calls of the model on the same latent and t,
@@ -959,12 +966,9 @@ class WanModel(nn.Module):
         if plain:
             return self.forward(x, t, context, seq_len), self.forward(x, t, context_null, seq_len)
         t = t.reshape(-1)
-        for _ in range(2):
-            cond = self._forward_one(x[0], t[0], context[0], seq_len, share='save')
-            uncond = self._forward_one(x[0], t[0], context_null[0], seq_len, share='reuse')
-            if not self._peer_transport_failed():       # (see forward: a refused peer copy sends the whole group back to the collective, once)
-                break
-        return [cond], [uncond]
+        return self._retry_without_peer_copies(lambda: ([self._forward_one(x[0], t[0], context[0], seq_len, share='save')],
+                                                        [self._forward_one(x[0], t[0], context_null[0], seq_len, share='reuse')]))
+
 
     def _peer_transport_failed(self):
         """once per forward (one 4-byte read per open window set — nothing at all on the default collective transport): did a peer copy

@@ -168,6 +168,71 @@ class WanT2V:
         mine = self.model([latent], t=t, context=context_null if self.cfgp.branch else context, seq_len=seq_len)[0]
         return self.cfgp.exchange(mine)
 
+    def _scheduler(self, sample_solver, sampling_steps, shift):
+        """-> (scheduler, timesteps on the device) of the reference's two solvers (text2video.py:186-207)"""
+        if sample_solver == 'unipc':
+            sample_scheduler = FlowUniPCMultistepScheduler(
+                num_train_timesteps=self.num_train_timesteps, shift=1, use_dynamic_shifting=False)
+            sample_scheduler.set_timesteps(sampling_steps, device=self.device, shift=shift)
+            return sample_scheduler, sample_scheduler.timesteps
+        if sample_solver == 'dpm++':
+            sample_scheduler = FlowDPMSolverMultistepScheduler(
+                num_train_timesteps=self.num_train_timesteps, shift=1, use_dynamic_shifting=False)
+            sampling_sigmas = get_sampling_sigmas(sampling_steps, shift)
+            timesteps, _ = retrieve_timesteps(sample_scheduler, device=self.device, sigmas=sampling_sigmas)
+            return sample_scheduler, timesteps
+        raise NotImplementedError("Unsupported solver.")
+
+    def _decode(self, x0, target_shape, offload_model):
+        """VAE decode of the final latent -> videos (None off rank 0), with the offload policy in front of it and one retry behind it;
+        sets self.last_offloaded: did the DiT's weights go to the host?"""
+        offloaded = False
+        if offload_model:
+            # reference text2video.py:257-259 moves the DiT to the host before the VAE decode to make room on an
+            # 80 GB device.  Here that is 28 GB over PCIe and back on the next call, for nothing, whenever the decode
+            # fits beside the resident model — which it does on 288 GB: the flag then only drops the DiT's activation
+            # workspace; the weights move only when the free memory would not hold 1.25 x the decode's estimated peak
+            # (MOVIIGEN_FORCE_OFFLOAD=1 restores the reference's unconditional move), and a decode that still runs out
+            # of memory is retried once with the DiT on the host.
+            self.model._ws = {}
+            torch.cuda.empty_cache()
+            free_b, _ = torch.cuda.mem_get_info(self.device)
+            need_b = self.vae.decode_peak_bytes(target_shape) if hasattr(self.vae, 'decode_peak_bytes') else 32 << 30
+            need_b = need_b * 5 // 4
+            if os.environ.get('MOVIIGEN_FORCE_OFFLOAD') == '1':
+                need_b = free_b + 1
+            if free_b > need_b:
+                logging.info(f'offload_model: {free_b / 2**30:.0f} GiB free >= {need_b / 2**30:.0f} GiB for the VAE decode '
+                             '-> the DiT stays resident (nothing is moved to the host)')
+            else:
+                self.model.cpu()
+                torch.cuda.empty_cache()
+                offloaded = True
+
+        def decode():
+            if self.vae_parallel:    # multi-GPU decode over all ranks, video assembled on rank 0: W bands (default), or the layer pipeline
+                out = self.vae.decode_pipelined(x0) if self.vae_parallel_kind == 'pipeline' else self.vae.decode_spatial(x0)
+                return out if self.rank == 0 else None
+            return self.vae.decode(x0) if self.rank == 0 else None
+        retry = False
+        try:
+            videos = decode()
+        except torch.cuda.OutOfMemoryError:
+            if not offload_model or offloaded or self.vae_parallel:      # (pipelined decode: one rank retrying alone would leave its peers in their send / recv)
+                raise
+            retry = True       # decided here, done BELOW: inside the handler the live exception's traceback still holds the failed decode's
+            #                    frames — its multi-GB fp32 activations — and neither model.cpu() nor empty_cache() could free them
+        if retry:
+            logging.warning('offload_model: the VAE decode ran out of memory beside the resident DiT -> moving the '
+                            'DiT to the host (reference text2video.py:257-259) and decoding again')
+            gc.collect()
+            self.model.cpu()
+            torch.cuda.empty_cache()
+            offloaded = True
+            videos = decode()
+        self.last_offloaded = offloaded
+        return videos
+
     def generate(self, input_prompt, size=(1280, 720), frame_num=81, shift=5.0, sample_solver='unipc',
                  sampling_steps=50, guide_scale=5.0, n_prompt="", seed=-1, offload_model=True,
                  noise=None, callback=None, step_cache=None, init_video=None, strength=1.0):
@@ -211,18 +276,7 @@ class WanT2V:
             assert tuple(noise.shape) == tuple(target_shape)
 
         with torch.no_grad():
-            if sample_solver == 'unipc':
-                sample_scheduler = FlowUniPCMultistepScheduler(
-                    num_train_timesteps=self.num_train_timesteps, shift=1, use_dynamic_shifting=False)
-                sample_scheduler.set_timesteps(sampling_steps, device=self.device, shift=shift)
-                timesteps = sample_scheduler.timesteps
-            elif sample_solver == 'dpm++':
-                sample_scheduler = FlowDPMSolverMultistepScheduler(
-                    num_train_timesteps=self.num_train_timesteps, shift=1, use_dynamic_shifting=False)
-                sampling_sigmas = get_sampling_sigmas(sampling_steps, shift)
-                timesteps, _ = retrieve_timesteps(sample_scheduler, device=self.device, sigmas=sampling_sigmas)
-            else:
-                raise NotImplementedError("Unsupported solver.")
+            sample_scheduler, timesteps = self._scheduler(sample_solver, sampling_steps, shift)
 
             latent = noise
             if init_video is not None:
@@ -252,51 +306,7 @@ class WanT2V:
                     callback(i, latent)
             if plan is not None:
                 self.model.drop_step_cache()
-            x0 = [latent]
-            offloaded = False
-            if offload_model:
-                # reference text2video.py:257-259 moves the DiT to the host before the VAE decode to make room on an
-                # 80 GB device.  Here that is 28 GB over PCIe and back on the next call, for nothing, whenever the decode
-                # fits beside the resident model — which it does on 288 GB: the flag then only drops the DiT's activation
-                # workspace; the weights move only when the free memory would not hold 1.25 x the decode's estimated peak
-                # (MOVIIGEN_FORCE_OFFLOAD=1 restores the reference's unconditional move), and a decode that still runs out
-                # of memory is retried once with the DiT on the host.
-                self.model._ws = {}
-                torch.cuda.empty_cache()
-                free_b, _ = torch.cuda.mem_get_info(self.device)
-                need_b = self.vae.decode_peak_bytes(target_shape) if hasattr(self.vae, 'decode_peak_bytes') else 32 << 30
-                need_b = need_b * 5 // 4
-                if os.environ.get('MOVIIGEN_FORCE_OFFLOAD') == '1':
-                    need_b = free_b + 1
-                if free_b > need_b:
-                    logging.info(f'offload_model: {free_b / 2**30:.0f} GiB free >= {need_b / 2**30:.0f} GiB for the VAE decode '
-                                 '-> the DiT stays resident (nothing is moved to the host)')
-                else:
-                    self.model.cpu()
-                    torch.cuda.empty_cache()
-                    offloaded = True
-            def decode():
-                if self.vae_parallel:    # multi-GPU decode over all ranks, video assembled on rank 0: W bands (default), or the layer pipeline
-                    out = self.vae.decode_pipelined(x0) if self.vae_parallel_kind == 'pipeline' else self.vae.decode_spatial(x0)
-                    return out if self.rank == 0 else None
-                return self.vae.decode(x0) if self.rank == 0 else None
-            retry = False
-            try:
-                videos = decode()
-            except torch.cuda.OutOfMemoryError:
-                if not offload_model or offloaded or self.vae_parallel:      # (pipelined decode: one rank retrying alone would leave its peers in their send / recv)
-                    raise
-                retry = True       # decided here, done BELOW: inside the handler the live exception's traceback still holds the failed decode's
-                #                    frames — its multi-GB fp32 activations — and neither model.cpu() nor empty_cache() could free them
-            if retry:
-                logging.warning('offload_model: the VAE decode ran out of memory beside the resident DiT -> moving the '
-                                'DiT to the host (reference text2video.py:257-259) and decoding again')
-                gc.collect()
-                self.model.cpu()
-                torch.cuda.empty_cache()
-                offloaded = True
-                videos = decode()
-            self.last_offloaded = offloaded
+            videos = self._decode([latent], target_shape, offload_model)
 
         del noise, latent, sample_scheduler
         if offload_model:

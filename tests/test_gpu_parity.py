@@ -651,6 +651,43 @@ def test_forward_pair_shares_block0_prefix_bit_equal(dev, monkeypatch):
     assert calls['attn'] - n0 == 4 * cfg['num_layers'] and torch.equal(pa[0], a) and torch.equal(pb[0], b)
 
 
+@pytest.mark.parametrize('cfg', [W.SMALL_DIT_HD128, W.TINY_DIT], ids=['hd128', 'hd32'])
+def test_dit_forward_launch_sequence(dev, monkeypatch, cfg):
+    """The library entry points one WanModel.forward calls, in order, at 48 tokens: the literal sequence, so that a change of the
+    Python that drives the kernels cannot add, drop or reorder a launch unnoticed (every launch of a block is paid 40 x 50 x 2 times
+    per video).  Second forward of a prompt = prelude + num_layers x block + tail: 15 launches per block at head_dim 128, 14 at
+    head_dim 32 (no K/V tile packing, the generic attention kernel).  The first forward of a new prompt adds the two text-embedding
+    GEMMs once and, per block, the cross-attention k|v GEMM, k's RMS-norm and (head_dim 128) the packing of K/V into tiles."""
+    import wan
+    from wan.backend import lib
+    m = wan.modules.WanModel(**cfg)
+    m.load_state_dict(W.make_dit_params(cfg, 0))
+    m.to(dev)
+    lat, ctx, t = W.randn((16, 2, 8, 12), 20).to(dev), W.randn((29, cfg['text_dim']), 30).to(dev), torch.tensor([999], device=dev)
+    names, real = [], lib.call
+    monkeypatch.setattr(lib, 'call', lambda name, *args: (names.append(name), real(name, *args))[1])
+
+    def forward():
+        names.clear()
+        m([lat], t=t, context=[ctx], seq_len=48)
+        return list(names)
+    first, second = forward(), forward()
+    hd128 = cfg['dim'] // cfg['num_heads'] == 128
+    ln, gemm, norm = 'mg_ln_modulate', 'mg_gemm_bf16', 'mg_rmsnorm_rope_bf16'
+    attn = 'mg_attn_fwd_bf16_hd128_prescaled' if hd128 else 'mg_attn_fwd_bf16_generic'
+    pack = ['mg_pack_kv_bf16'] if hd128 else []
+    prelude = ['mg_patchify_bf16', gemm, 'mg_sinusoid_embed', 'mg_gemv_f32', 'mg_gemv_f32', 'mg_gemv_f32', 'mg_add_rows_f32',
+               'mg_add_rows_f32']
+    self_attn = [ln, gemm, norm, norm] + pack + [attn, gemm]
+    cross_attn = [ln, gemm, norm, attn, gemm]
+    ffn = [ln, gemm, gemm]
+    tail = [ln, 'mg_head_gemm_f32', 'mg_unpatchify_f32']
+    assert len(self_attn + cross_attn + ffn) == (15 if hd128 else 14)
+    assert second == prelude + cfg['num_layers'] * (self_attn + cross_attn + ffn) + tail
+    cross_kv = [gemm, norm] + pack                      # made when block i first meets the prompt, in front of its cross-attention
+    assert first == prelude + [gemm, gemm] + cfg['num_layers'] * (self_attn + cross_kv + cross_attn + ffn) + tail
+
+
 # ------------------------------------------------------------------------------------------------
 # schedulers on the GPU (fused lincomb kernel) vs the reference trajectories
 # ------------------------------------------------------------------------------------------------
