@@ -458,6 +458,36 @@ int mg_image_to_u8(const float* image, int H, int W, float lo, float hi, uint8_t
  * 17 taps per axis), or H or T above 65535.  frames needs no alignment; video is written once, every element. */
 int mg_video_from_u8(const uint8_t* frames, int T, int H0, int W0, int H, int W, float* video, void* stream);
 
+/* Masked video-to-video (additions to ABI 9; not in the reference): WanT2V.inpaint keeps part of an existing clip and regenerates the rest.
+ * Masks are hard: a byte is 0 (keep) or non-zero (regenerate).  The four functions use no device memory of their own and no atomics; every
+ * output element is written by one thread: run-to-run identical.  A non-positive size is MG_ERR_SHAPE (checked before the pointers), a
+ * null pointer MG_ERR_ARG.
+ *
+ * mg_mask_from_u8: the user's mask [Tm][H0][W0] (Tm == 1: one mask for every frame, else Tm >= T and the first T frames are read) -> the
+ * pixel mask pm [T][H][W] through the geometry and the filter of mg_video_from_u8, so that mask and frames stay aligned:
+ *   pm[t][y][x] = 0 for t < keep_frames, else (r >= 127.5f) ? 1 : 0, r = the fp32 sum mg_video_from_u8 forms for one channel of frame t
+ *   (frame 0 when Tm == 1) holding the mask's bytes: the same taps in the same order, rows outer, columns inner.
+ * With (H0, W0) == (H, W) r is the byte itself: pm = (mask >= 128) exactly.  MG_ERR_SHAPE as for mg_video_from_u8, and for Tm outside
+ * {1} u [T, inf) or keep_frames outside [0, T].  Every byte of pm is written once. */
+int mg_mask_from_u8(const uint8_t* mask, int Tm, int H0, int W0, int T, int H, int W, int keep_frames, uint8_t* pm, void* stream);
+
+/* pm [T][H][W] -> the latent-grid mask lm [(T-1)/st + 1][H/sh][W/sw] of a causal VAE with strides (st, sh, sw): lm[j][y][x] = 1 when any
+ * byte of pm is non-zero over rows sh y .. sh y + sh - 1, columns sw x .. sw x + sw - 1 and frames {0} for j = 0, st (j-1) + 1 .. st j for
+ * j >= 1, else 0: a latent cell is kept only if every pixel under it is kept.  MG_ERR_SHAPE unless (T-1) % st == 0, H % sh == 0, W % sw == 0. */
+int mg_mask_to_latent_u8(const uint8_t* pm, int T, int H, int W, int st, int sh, int sw, uint8_t* lm, void* stream);
+
+/* latent [C][thw] fp32, IN PLACE, lm [thw] shared by the C channels; z0 and noise like latent:
+ *   lm == 0: latent = c0 z0 + c1 noise, the bits mg_lincomb4_f32 writes for the two terms (z0, c0), (noise, c1) (fma(c1, noise, c0 z0));
+ *   lm != 0: the element keeps its bits.
+ * A select: a non-finite value of the side not chosen does not reach the result.  16-byte accesses when latent, z0 and noise are 16-byte
+ * aligned, element by element otherwise; any thw. */
+int mg_masked_renoise_f32(float* latent, const float* z0, const float* noise, const uint8_t* lm, float c0, float c1, int C, int64_t thw,
+                          void* stream);
+
+/* video [3][T][hw] fp32, IN PLACE, src of the same shape, pm [T][hw]: video = src where pm == 0, untouched elsewhere (a select, as above).
+ * 16-byte accesses when video and src are 16-byte aligned; any hw. */
+int mg_mask_composite_f32(float* video, const float* src, const uint8_t* pm, int T, int64_t hw, void* stream);
+
 /* time_conv channel halves -> interleaved frames (vae.py:133-137):
  * x [T][H][W][2C] -> out [2T][H][W][C], frame 2t from channels [0,C), 2t+1 from [C,2C). */
 int mg_vae_time_interleave_f32(const float* x, int T, int64_t HW, int C, float* out, void* stream);

@@ -97,3 +97,54 @@ static inline int mg_check_launch() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? MG_OK : MG_ERR_LAUNCH;
 }
+
+// In-place masked overwrite of x [C][n] fp32 (total = C n) under a byte mask [n] shared by the C planes: x[i] = f(i) where mask[i % n] == 0,
+// the element keeps its bits elsewhere.  A select, not a blend: the side not chosen never enters the arithmetic of the result.
+// F has one(i) -> float and vec(i) -> f32x4_t (i % 4 == 0, its sources 16-byte aligned) for the new value of flat element i.
+// nvec groups of four elements go as 16-byte accesses (the launcher passes 0 when a pointer is not 16-byte aligned), the elements from
+// 4 nvec on one by one.  A group may straddle a plane boundary when n % 4 != 0: its mask bytes are then read one by one with the wrap;
+// mask_dword = (n % 4 == 0 and mask 4-byte aligned) reads them as one dword.  A group with nothing to overwrite is neither loaded nor
+// stored, one with everything to overwrite does not load x.  (mg_masked_renoise_f32, mg_mask_composite_f32)
+template <class F>
+__global__ __launch_bounds__(256) void masked_overwrite_kernel(float* __restrict__ x, const uint8_t* __restrict__ mask, int64_t n, int64_t total,
+                                                               int64_t nvec, bool mask_dword, F f) {
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t g = tid; g < nvec; g += stride) {
+        const int64_t i = 4 * g;
+        int64_t p = i % n;
+        bool keep[4];
+        if (mask_dword) {
+            const uint32_t m = *reinterpret_cast<const uint32_t*>(mask + p);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) keep[e] = ((m >> (8 * e)) & 0xffu) != 0;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                keep[e] = mask[p] != 0;
+                if (++p == n) p = 0;
+            }
+        }
+        const bool any_keep = keep[0] | keep[1] | keep[2] | keep[3], all_keep = keep[0] & keep[1] & keep[2] & keep[3];
+        if (all_keep) continue;
+        f32x4_t v = f.vec(i);
+        if (any_keep) {
+            const f32x4_t xv = *reinterpret_cast<const f32x4_t*>(x + i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = keep[e] ? xv[e] : v[e];
+        }
+        *reinterpret_cast<f32x4_t*>(x + i) = v;
+    }
+    for (int64_t i = 4 * nvec + tid; i < total; i += stride)
+        if (mask[i % n] == 0) x[i] = f.one(i);
+}
+
+// the launch of masked_overwrite_kernel: `aligned16` = x and every source of f are 16-byte aligned
+template <class F>
+static inline int mg_launch_masked_overwrite(float* x, const uint8_t* mask, int64_t n, int64_t total, bool aligned16, F f, void* stream) {
+    const int64_t nvec = aligned16 ? total / 4 : 0, work = nvec + (total - 4 * nvec);
+    int64_t grid = (work + 255) / 256;
+    if (grid > 8192) grid = 8192;
+    hipLaunchKernelGGL(masked_overwrite_kernel<F>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, mask, n, total, nvec,
+                       (n & 3) == 0 && ((uintptr_t)mask & 3) == 0, f);
+    return mg_check_launch();
+}

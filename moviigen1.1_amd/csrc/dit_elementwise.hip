@@ -640,6 +640,69 @@ extern "C" int mg_lincomb4_f32(float* out, int64_t n, const float* x0, float c0,
 }
 
 // ---------------------------------------------------------------------------------------------
+// Masked video-to-video (WanT2V.inpaint; definitions in the header): the pixel mask -> the latent-grid mask, and the overwrite of the
+// kept latent cells with c0 z0 + c1 noise behind every scheduler step
+// ---------------------------------------------------------------------------------------------
+// one thread per latent cell: the OR over its footprint, st (or 1) frames x sh rows x sw bytes; neighbouring threads read neighbouring
+// sw-byte runs of the same pixel row.  `dword` (sw % 4 == 0, W % 4 == 0, pm 4-byte aligned): the runs are read as dwords.
+__global__ __launch_bounds__(256) void mask_to_latent_kernel(const uint8_t* __restrict__ pm, int H, int W, int st, int sh, int sw, int Hl, int Wl,
+                                                             int64_t total, bool dword, uint8_t* __restrict__ lm) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int x = (int)(i % Wl);
+        const int64_t r = i / Wl;
+        const int y = (int)(r % Hl), j = (int)(r / Hl);
+        const int t0 = j ? st * (j - 1) + 1 : 0, nt = j ? st : 1;        // the causal VAE's grouping: latent frame 0 is pixel frame 0 alone
+        uint32_t acc = 0;
+        for (int t = t0; t < t0 + nt; ++t)
+            for (int dy = 0; dy < sh; ++dy) {
+                const uint8_t* row = pm + ((int64_t)t * H + (int64_t)sh * y + dy) * W + (int64_t)sw * x;
+                if (dword)
+                    for (int k = 0; k < sw / 4; ++k) acc |= reinterpret_cast<const uint32_t*>(row)[k];
+                else
+                    for (int k = 0; k < sw; ++k) acc |= row[k];
+            }
+        lm[i] = acc ? 1 : 0;
+    }
+}
+
+extern "C" int mg_mask_to_latent_u8(const uint8_t* pm, int T, int H, int W, int st, int sh, int sw, uint8_t* lm, void* stream) {
+    if (T <= 0 || H <= 0 || W <= 0 || st <= 0 || sh <= 0 || sw <= 0) return MG_ERR_SHAPE;
+    if ((T - 1) % st || H % sh || W % sw) return MG_ERR_SHAPE;
+    if (!pm || !lm) return MG_ERR_ARG;
+    const int Hl = H / sh, Wl = W / sw;
+    const int64_t total = (int64_t)((T - 1) / st + 1) * Hl * Wl;
+    int64_t grid = (total + 255) / 256;
+    if (grid > 8192) grid = 8192;
+    hipLaunchKernelGGL(mask_to_latent_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, pm, H, W, st, sh, sw, Hl, Wl, total,
+                       (sw & 3) == 0 && (W & 3) == 0 && ((uintptr_t)pm & 3) == 0, lm);
+    return mg_check_launch();
+}
+
+// the new value of a kept cell: the two-term case of lincomb4_kernel, a = c0 x0; a += c1 x1, which the compiler contracts to one
+// multiply and one fused multiply-add — written out here so that the bits do not depend on the contraction mode of this expression
+struct RenoiseValue {
+    const float* z0;
+    const float* noise;
+    float c0, c1;
+    __device__ float one(int64_t i) const { return __builtin_fmaf(c1, noise[i], c0 * z0[i]); }
+    __device__ f32x4_t vec(int64_t i) const {
+        const f32x4_t z = *reinterpret_cast<const f32x4_t*>(z0 + i), e = *reinterpret_cast<const f32x4_t*>(noise + i);
+        f32x4_t v;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = __builtin_fmaf(c1, e[k], c0 * z[k]);
+        return v;
+    }
+};
+
+extern "C" int mg_masked_renoise_f32(float* latent, const float* z0, const float* noise, const uint8_t* lm, float c0, float c1, int C, int64_t thw,
+                                     void* stream) {
+    if (C <= 0 || thw <= 0) return MG_ERR_SHAPE;
+    if (!latent || !z0 || !noise || !lm) return MG_ERR_ARG;
+    const bool aligned16 = (((uintptr_t)latent | (uintptr_t)z0 | (uintptr_t)noise) & 15) == 0;
+    return mg_launch_masked_overwrite(latent, lm, thw, (int64_t)C * thw, aligned16, RenoiseValue{z0, noise, c0, c1}, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
 // x[r][c] += y[r][c] * gate[c]   (x fp32 residual stream, y bf16, gate fp32 or NULL = 1): the gated residual of
 // model.py:301-302,306,308-309 as its own kernel — used when the producer of y is not one of this library's GEMMs
 // (a caller-replaced WanSelfAttention.forward, the operator seam of text2video.py:97-100); the GEMM epilogue

@@ -1013,18 +1013,79 @@ __global__ __launch_bounds__(256) void video_from_u8_kernel(const uint8_t* __res
     out[2 * total + i] = a2 / 127.5f - 1.f;
 }
 
-extern "C" int mg_video_from_u8(const uint8_t* frames, int T, int H0, int W0, int H, int W, float* video, void* stream) {
-    if (T <= 0 || H0 <= 0 || W0 <= 0 || H <= 0 || W <= 0) return MG_ERR_SHAPE;      // (first: an empty tensor has no address)
-    if (!frames || !video) return MG_ERR_ARG;
+// the cover / crop geometry of the ingest (definition in the header) and its MG_ERR_SHAPE rules: (oy, ox) the crop origin in the resized
+// image, sy / sx = input / resized extent
+struct U8Cover { int oy, ox; double sy, sx; };
+static int u8_cover(int T, int H0, int W0, int H, int W, U8Cover* g) {
     const double sh = (double)H / H0, sw = (double)W / W0, s = sh > sw ? sh : sw;
     const double hs_d = floor(H0 * s + 0.5), ws_d = floor(W0 * s + 0.5);
     if (hs_d > 8.0 * H0 || ws_d > 8.0 * W0 || hs_d > 0x7fffffff || ws_d > 0x7fffffff) return MG_ERR_SHAPE;      // more than 8x up
     const int Hs = hs_d > H ? (int)hs_d : H, Ws = ws_d > W ? (int)ws_d : W;
     if (H0 > 8 * (int64_t)Hs || W0 > 8 * (int64_t)Ws) return MG_ERR_SHAPE;              // more than 8x down: above 17 taps per axis
     if (H > 65535 || T > 65535) return MG_ERR_SHAPE;                                     // grid dimensions y, z
-    hipLaunchKernelGGL(video_from_u8_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)H, (unsigned)T), dim3(256), 0, (hipStream_t)stream, frames, T, H0, W0, H, W, (Hs - H) / 2, (Ws - W) / 2,
-                       (double)H0 / Hs, (double)W0 / Ws, video);
+    *g = U8Cover{(Hs - H) / 2, (Ws - W) / 2, (double)H0 / Hs, (double)W0 / Ws};
+    return MG_OK;
+}
+
+extern "C" int mg_video_from_u8(const uint8_t* frames, int T, int H0, int W0, int H, int W, float* video, void* stream) {
+    if (T <= 0 || H0 <= 0 || W0 <= 0 || H <= 0 || W <= 0) return MG_ERR_SHAPE;      // (first: an empty tensor has no address)
+    if (!frames || !video) return MG_ERR_ARG;
+    U8Cover g;
+    if (const int rc = u8_cover(T, H0, W0, H, W, &g)) return rc;
+    hipLaunchKernelGGL(video_from_u8_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)H, (unsigned)T), dim3(256), 0, (hipStream_t)stream, frames, T, H0, W0, H, W, g.oy, g.ox,
+                       g.sy, g.sx, video);
     return mg_check_launch();
+}
+
+// ---- masked video-to-video (WanT2V.inpaint; definitions in the header): the pixel mask through the ingest's filter, and the copy of the
+// kept pixels from the source clip behind the decode ----
+// video_from_u8_kernel for a one-channel image, thresholded: the same taps, weights and summation order, so r is the sum the ingest
+// forms for a channel holding these bytes.  frame_stride = 0: one mask for every frame.  Frames below keep_frames are written 0 unread.
+__global__ __launch_bounds__(256) void mask_from_u8_kernel(const uint8_t* __restrict__ mask, int64_t frame_stride, int H0, int W0, int H, int W, int oy, int ox,
+                                                           double sy, double sx, int keep_frames, uint8_t* __restrict__ pm) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, t = blockIdx.z;
+    if (x >= W) return;
+    const int64_t i = ((int64_t)t * H + y) * W + x;
+    if (t < keep_frames) {
+        pm[i] = 0;
+        return;
+    }
+    const U8Taps ay = u8_axis_taps(y + oy, H0, sy), ax = u8_axis_taps(x + ox, W0, sx);
+    const uint8_t* const fr = mask + (int64_t)t * frame_stride;
+    float r = 0.f;
+    for (int j = 0; j < ay.n; ++j) {                                   // rows outer, columns inner: the ingest's order
+        const float wy = u8_tap_weight(ay, j) * ay.rnorm;
+        const uint8_t* row = fr + (int64_t)(ay.lo + j) * W0 + ax.lo;
+        for (int k = 0; k < ax.n; ++k) {
+            const float w = wy * (u8_tap_weight(ax, k) * ax.rnorm);
+            r += w * (float)row[k];
+        }
+    }
+    pm[i] = r >= 127.5f ? 1 : 0;
+}
+
+extern "C" int mg_mask_from_u8(const uint8_t* mask, int Tm, int H0, int W0, int T, int H, int W, int keep_frames, uint8_t* pm, void* stream) {
+    if (Tm <= 0 || T <= 0 || H0 <= 0 || W0 <= 0 || H <= 0 || W <= 0) return MG_ERR_SHAPE;
+    if ((Tm != 1 && Tm < T) || keep_frames < 0 || keep_frames > T) return MG_ERR_SHAPE;
+    if (!mask || !pm) return MG_ERR_ARG;
+    U8Cover g;
+    if (const int rc = u8_cover(T, H0, W0, H, W, &g)) return rc;
+    hipLaunchKernelGGL(mask_from_u8_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)H, (unsigned)T), dim3(256), 0, (hipStream_t)stream, mask,
+                       Tm == 1 ? (int64_t)0 : (int64_t)H0 * W0, H0, W0, H, W, g.oy, g.ox, g.sy, g.sx, keep_frames, pm);
+    return mg_check_launch();
+}
+
+struct CompositeValue {
+    const float* src;
+    __device__ float one(int64_t i) const { return src[i]; }
+    __device__ f32x4_t vec(int64_t i) const { return *reinterpret_cast<const f32x4_t*>(src + i); }
+};
+
+extern "C" int mg_mask_composite_f32(float* video, const float* src, const uint8_t* pm, int T, int64_t hw, void* stream) {
+    if (T <= 0 || hw <= 0) return MG_ERR_SHAPE;
+    if (!video || !src || !pm) return MG_ERR_ARG;
+    const bool aligned16 = (((uintptr_t)video | (uintptr_t)src) & 15) == 0;
+    return mg_launch_masked_overwrite(video, pm, (int64_t)T * hw, (int64_t)3 * T * hw, aligned16, CompositeValue{src}, stream);
 }
 
 __global__ void time_interleave_kernel(const float* __restrict__ x, int T, int64_t hw, int C, float* __restrict__ out) {

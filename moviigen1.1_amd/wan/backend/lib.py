@@ -74,6 +74,10 @@ SIGNATURES = {
     'mg_vae_latent_out_f32': [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp],
     'mg_video_to_u8': [c_vp, c_int, c_int, c_int, c_f32, c_f32, c_vp, c_vp],
     'mg_video_from_u8': [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp],
+    'mg_mask_from_u8': [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp],
+    'mg_mask_to_latent_u8': [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp],
+    'mg_masked_renoise_f32': [c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_int, c_i64, c_vp],
+    'mg_mask_composite_f32': [c_vp, c_vp, c_vp, c_int, c_i64, c_vp],
     'mg_lora_merge': [c_vp, c_int, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_int, c_vp],
     'mg_comm_unique_id': [c_vp],
     'mg_comm_create': [c_vp, c_int, c_int, c_vp],

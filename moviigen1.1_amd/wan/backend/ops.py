@@ -561,6 +561,60 @@ def video_from_u8(frames, H, W, out=None):
     return out
 
 
+def mask_from_u8(mask, T, H, W, keep_frames=0, out=None):
+    """uint8 mask [Tm,H0,W0] (Tm == 1 or >= T; >= 128 after the resize = regenerate) -> the pixel mask [T,H,W] uint8 0/1 through the geometry and
+    filter of video_from_u8; frames below keep_frames are 0 = kept (mg_mask_from_u8; the definition is in include/moviigen_hip.h)."""
+    _chk(mask, torch.uint8, 'mask'); _chk(out, torch.uint8, 'out')
+    if mask.dim() != 3 or not mask.is_contiguous():
+        raise lib.MoviigenHipError(f'mask must be a contiguous uint8 [Tm, H0, W0] tensor, got {tuple(mask.shape)}')
+    Tm, H0, W0 = mask.shape
+    if out is None:
+        out = torch.empty(int(T), int(H), int(W), dtype=torch.uint8, device=mask.device)
+    elif tuple(out.shape) != (int(T), int(H), int(W)) or not out.is_contiguous():
+        raise lib.MoviigenHipError(f'mask_from_u8: out must be a contiguous {(int(T), int(H), int(W))} tensor, got {tuple(out.shape)}')
+    lib.call('mg_mask_from_u8', _p(mask), Tm, H0, W0, int(T), int(H), int(W), int(keep_frames), _p(out), _st())
+    return out
+
+
+def mask_to_latent(pm, stride):
+    """pixel mask [T,H,W] uint8 -> the latent-grid mask [(T-1)/st+1, H/sh, W/sw] uint8 0/1 of a causal VAE with `stride` = (st, sh, sw): the OR
+    over every pixel under a latent cell (mg_mask_to_latent_u8)."""
+    _chk(pm, torch.uint8, 'pm')
+    if pm.dim() != 3 or not pm.is_contiguous():
+        raise lib.MoviigenHipError(f'pm must be a contiguous uint8 [T, H, W] tensor, got {tuple(pm.shape)}')
+    T, H, W = pm.shape
+    st, sh, sw = (int(v) for v in stride)
+    if min(st, sh, sw) <= 0:
+        raise lib.MoviigenHipError(f'mask_to_latent: stride must be positive, got {(st, sh, sw)}')
+    lm = torch.empty((T - 1) // st + 1, H // sh, W // sw, dtype=torch.uint8, device=pm.device)
+    lib.call('mg_mask_to_latent_u8', _p(pm), T, H, W, st, sh, sw, _p(lm), _st())
+    return lm
+
+
+def masked_renoise(latent, z0, noise, lm, c0, c1):
+    """latent [C, ...] fp32 IN PLACE: c0 z0 + c1 noise (the bits of lincomb) where lm [...] uint8 is 0, untouched where it is not
+    (mg_masked_renoise_f32)."""
+    for n, t in (('latent', latent), ('z0', z0), ('noise', noise)):
+        _chk(t, torch.float32, n)
+    _chk(lm, torch.uint8, 'lm')
+    if not (latent.is_contiguous() and z0.is_contiguous() and noise.is_contiguous() and lm.is_contiguous()) or latent.dim() < 2 \
+            or z0.shape != latent.shape or noise.shape != latent.shape or lm.numel() * latent.shape[0] != latent.numel():
+        raise lib.MoviigenHipError(f'masked_renoise: latent {tuple(latent.shape)}, z0 {tuple(z0.shape)}, noise {tuple(noise.shape)}, lm {tuple(lm.shape)}')
+    lib.call('mg_masked_renoise_f32', _p(latent), _p(z0), _p(noise), _p(lm), float(c0), float(c1), latent.shape[0], lm.numel(), _st())
+    return latent
+
+
+def mask_composite(video, src, pm):
+    """video [3,T,H,W] fp32 IN PLACE: src where pm [T,H,W] uint8 is 0, untouched where it is not (mg_mask_composite_f32)."""
+    _chk(video, torch.float32, 'video'); _chk(src, torch.float32, 'src'); _chk(pm, torch.uint8, 'pm')
+    if video.dim() != 4 or video.shape[0] != 3 or src.shape != video.shape or tuple(pm.shape) != tuple(video.shape[1:]) \
+            or not (video.is_contiguous() and src.is_contiguous() and pm.is_contiguous()):
+        raise lib.MoviigenHipError(f'mask_composite: video {tuple(video.shape)}, src {tuple(src.shape)}, pm {tuple(pm.shape)}')
+    T = video.shape[1]
+    lib.call('mg_mask_composite_f32', _p(video), _p(src), _p(pm), T, video.shape[2] * video.shape[3], _st())
+    return video
+
+
 def gate_residual(x, y, gate=None):
     """x [rows, dim] fp32 += y [rows, dim] bf16 * gate [dim] fp32 (None = 1)."""
     _chk(x, torch.float32, 'x'); _chk(y, torch.bfloat16, 'y'); _chk(gate, torch.float32, 'gate')

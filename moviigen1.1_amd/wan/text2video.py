@@ -12,6 +12,7 @@ of `[len<=512, 4096]` tensors, and `input_prompt` / `n_prompt` may also be pre-c
 """
 import contextlib
 import gc
+import inspect
 import logging
 import math
 import os
@@ -36,6 +37,14 @@ def v2v_steps(sampling_steps, strength):
         raise ValueError(f'strength must be in (0, 1], got {strength!r}')
     n_run = min(max(int(sampling_steps * float(strength)), 1), sampling_steps)
     return n_run, sampling_steps - n_run
+
+
+class MaskedEdit:
+    """what `WanT2V.inpaint` carries through the sampling loop: the pixel mask pm [T, H, W] and the latent-grid mask lm (uint8, 1 = regenerate,
+    0 = keep), and, filled in by `start_latent(keep=)`, the source clip and its encoding z0."""
+
+    def __init__(self, pm, lm):
+        self.pm, self.lm, self.clip, self.z0 = pm, lm, None, None
 
 
 class WanT2V:
@@ -143,9 +152,13 @@ class WanT2V:
                              f'{tuple(init_video.shape)}')
         return init_video[:, :frame_num].to(self.device, torch.float32).contiguous()
 
-    def start_latent(self, init_video, size, frame_num, noise, sigma):
-        """the latent a video-to-video run starts from: (1 - sigma) z0 + sigma noise with z0 = vae.encode(init_clip(init_video)), one fused launch."""
-        z0 = self.vae.encode([self.init_clip(init_video, size, frame_num)])[0]
+    def start_latent(self, init_video, size, frame_num, noise, sigma, keep=None):
+        """the latent a video-to-video run starts from: (1 - sigma) z0 + sigma noise with z0 = vae.encode(init_clip(init_video)), one fused launch.
+        keep: a MaskedEdit that receives the clip and z0 (a masked run reads both again; nothing is encoded twice)."""
+        clip = self.init_clip(init_video, size, frame_num)
+        z0 = self.vae.encode([clip])[0]
+        if keep is not None:
+            keep.clip, keep.z0 = clip, z0
         if tuple(z0.shape) != tuple(noise.shape):
             raise ValueError(f'init_video encodes to {tuple(z0.shape)}, the latent of this call is {tuple(noise.shape)}')
         # (also what makes the strength-1 start exact: 0 x finite = 0, and 0 + 1 x noise = noise)
@@ -254,6 +267,63 @@ class WanT2V:
             known before the loop, the same on every rank and for both guidance branches.  The first step that runs is always computed.
             `self.last_step_plan` holds the plan of the last call (None without a step cache); the residuals are dropped when the loop ends.
             Threshold 0 and an all-True plan give the bits of step_cache=None."""
+        return self._sample(input_prompt, size, frame_num, shift, sample_solver, sampling_steps, guide_scale, n_prompt, seed, offload_model,
+                            noise, callback, step_cache, init_video, strength, edit=None)
+
+    def masked_edit(self, init_video, mask, keep_frames, size, frame_num):
+        """`inpaint`'s mask / keep_frames -> MaskedEdit(pm, lm): the mask through the cover / crop geometry of the frames (ops.mask_from_u8), the
+        first keep_frames frames kept whole, then the OR over every pixel under a latent cell (ops.mask_to_latent)."""
+        W_, H_ = size
+        keep_frames = int(keep_frames)
+        if not 0 <= keep_frames <= frame_num:
+            raise ValueError(f'keep_frames must be in [0, {frame_num}], got {keep_frames}')
+        if mask is None:
+            if keep_frames == 0:
+                raise ValueError('inpaint needs a mask or keep_frames > 0: there is nothing to keep')
+            mask = torch.full((1, H_, W_), 255, dtype=torch.uint8, device=self.device)       # everything behind the kept frames is regenerated
+        else:
+            mask = torch.as_tensor(mask)
+            if mask.dtype == torch.bool:
+                mask = mask.to(torch.uint8) * 255
+            if mask.dim() == 2:
+                mask = mask.unsqueeze(0)
+            if mask.dtype != torch.uint8 or mask.dim() != 3 or not (mask.shape[0] == 1 or mask.shape[0] >= frame_num):
+                raise ValueError(f'mask must be uint8 or bool, [Tm, H0, W0] with Tm == 1 or Tm >= {frame_num}, or [H0, W0]; got {mask.dtype} {tuple(mask.shape)}')
+            # the spatial size of init_video: the mask goes through the same resize and crop as the frames, so the two stay aligned
+            src = init_video if torch.is_tensor(init_video) else torch.as_tensor(init_video)
+            hw0 = tuple(src.shape[1:3]) if src.dim() == 4 and src.dtype == torch.uint8 else (H_, W_)
+            if tuple(mask.shape[1:]) != hw0:
+                raise ValueError(f'mask is {tuple(mask.shape[1:])}, init_video is {hw0}: the mask must have the spatial size of init_video')
+            mask = mask[:frame_num].to(self.device).contiguous()
+        pm = ops.mask_from_u8(mask, frame_num, H_, W_, keep_frames)
+        return MaskedEdit(pm, ops.mask_to_latent(pm, self.vae_stride))
+
+    def inpaint(self, input_prompt, init_video, mask=None, keep_frames=0, strength=1.0, **kw):
+        """Masked video-to-video (NOT part of the reference): keep part of `init_video` and regenerate the rest.  `kw` are `generate`'s other
+        arguments (size, frame_num, shift, sample_solver, sampling_steps, guide_scale, n_prompt, seed, offload_model, noise, callback, step_cache).
+
+        mask: uint8 or bool, tensor or array, [Tm, H0, W0] (Tm == 1: one mask for every frame, or Tm >= frame_num: the first frame_num are used)
+            or [H0, W0], with the spatial size of init_video (the frame size of uint8 frames, `size` for a float clip); >= 128 / True =
+            regenerate, below = keep.  Hard masks only: the resized mask is thresholded at 127.5 again.
+        keep_frames = k: the first k pixel frames are kept whole (continuation); with mask=None everything behind them is regenerated.
+        strength: as in `generate`; the regenerated region starts from (1 - sigma) z0 + sigma noise like every video-to-video start.
+
+        The latent blend with the start noise re-used: a latent cell is kept only if every pixel under it is kept (lm); after every scheduler
+        step, which leaves the latent at sigma_{i+1}, the kept cells are overwritten with (1 - sigma_{i+1}) z0 + sigma_{i+1} noise
+        (ops.masked_renoise, before `callback`), so the solver's history holds what the model saw and, sigma ending in 0, the kept cells end
+        as z0.  After the decode the kept PIXELS are copied from the source clip (ops.mask_composite): a kept pixel of the result is the
+        source pixel bit for bit.  Every rank does the same element-wise passes on its whole latent: no collective is added.  An all-regenerate
+        mask gives the bits of `generate(init_video=, strength=)`."""
+        if init_video is None:
+            raise ValueError('inpaint needs init_video: there is nothing to keep')
+        args = inspect.signature(self.generate).bind(input_prompt, init_video=init_video, strength=strength, **kw)
+        args.apply_defaults()
+        edit = self.masked_edit(init_video, mask, keep_frames, args.arguments['size'], args.arguments['frame_num'])
+        return self._sample(edit=edit, **args.arguments)
+
+    def _sample(self, input_prompt, size, frame_num, shift, sample_solver, sampling_steps, guide_scale, n_prompt, seed, offload_model,
+                noise, callback, step_cache, init_video, strength, edit):
+        """the body of `generate` and `inpaint`; edit: None, or inpaint's MaskedEdit"""
         n_run, i0 = v2v_steps(sampling_steps, strength)
         if init_video is None and i0:
             raise ValueError('strength < 1 needs init_video: there is nothing to start from')
@@ -281,8 +351,10 @@ class WanT2V:
             latent = noise
             if init_video is not None:
                 sample_scheduler.set_begin_index(i0)
-                latent = self.start_latent(init_video, size, frame_num, noise, sample_scheduler.sigmas[i0].item() if i0 else 1.0)
+                keep = {} if edit is None else {'keep': edit}        # (`generate` calls the five-argument form: a replaced start_latent keeps serving it)
+                latent = self.start_latent(init_video, size, frame_num, noise, sample_scheduler.sigmas[i0].item() if i0 else 1.0, **keep)
             timesteps_host = timesteps.tolist()          # ONE sync for the whole loop
+            sigmas_host = sample_scheduler.sigmas.tolist() if edit is not None else None        # (steps + 1 entries, the last one 0)
             if next(self.model.parameters()).device != self.device:     # only after a real offload (a no-op move would
                 self.model.to(self.device)                               # still drop the fused-weight views: 28 GB re-packed)
             noise_pred = torch.empty_like(latent)
@@ -302,11 +374,15 @@ class WanT2V:
                 ops.cfg_combine(noise_pred, uncond, cond, guide_scale)
                 latent = sample_scheduler.step(noise_pred.unsqueeze(0), t_host, latent.unsqueeze(0),
                                                return_dict=False, generator=seed_g)[0].squeeze(0)
+                if edit is not None:        # the step left the latent at sigma_{i+1}: put the kept cells back at that noise level
+                    ops.masked_renoise(latent, edit.z0, noise, edit.lm, 1.0 - sigmas_host[i + 1], sigmas_host[i + 1])
                 if callback is not None:
                     callback(i, latent)
             if plan is not None:
                 self.model.drop_step_cache()
             videos = self._decode([latent], target_shape, offload_model)
+            if edit is not None and videos is not None:     # on the rank that holds the video: kept pixels are the source's, bit for bit
+                ops.mask_composite(videos[0], edit.clip, edit.pm)
 
         del noise, latent, sample_scheduler
         if offload_model:

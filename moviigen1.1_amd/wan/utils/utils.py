@@ -60,6 +60,19 @@ def load_video(path):
     return np.ascontiguousarray(frames)
 
 
+def load_mask(path):
+    """a mask from disk -> uint8 [T, H, W] or [H, W] (numpy), what `WanT2V.inpaint(mask=...)` takes: >= 128 = regenerate.  A `.npy` file
+    holds the mask itself; every other file is read by `load_video` and gives [T, H, W], the per-pixel maximum of the three channels."""
+    if not osp.exists(path):
+        raise FileNotFoundError(f'load_mask: {path} does not exist')
+    if osp.splitext(path)[1].lower() != '.npy':
+        return np.ascontiguousarray(load_video(path).max(axis=3))
+    mask = np.load(path, allow_pickle=False)
+    if mask.dtype != np.uint8 or mask.ndim not in (2, 3) or min(mask.shape) < 1:
+        raise ValueError(f'load_mask: {path} holds {mask.dtype} {mask.shape}, expected a uint8 mask [T, H, W] or [H, W]')
+    return np.ascontiguousarray(mask)
+
+
 def cache_video(tensor, save_file=None, fps=30, suffix='.mp4', nrow=8, normalize=True, value_range=(-1, 1), retry=5):
     if not normalize:
         raise NotImplementedError('the reference always calls cache_video with normalize=True')

@@ -12,6 +12,8 @@ must equal the world size as in the reference), `--use_prompt_extend` is not bui
 `--t5_fsdp` / `--t5_cpu` are accepted (the 9.4 GB encoder is simply replicated on the GPU).  Extra:
 `--cfg_parallel`, `--vae_parallel` (this engine's multi-GPU layouts),
 `--init_video FILE` / `--strength F` (a video-to-video start, `WanT2V.generate(init_video=, strength=)`),
+`--mask FILE` / `--keep_frames N` (with `--init_video`: masked video-to-video, `WanT2V.inpaint` — keep what the mask leaves out and / or
+the first N frames, regenerate the rest),
 `--lora PATH[:STRENGTH]` (repeatable: LoRA adapters merged into the DiT weights on the device, `WanModel.load_lora`),
 `--step_cache THRESH` / `--step_cache_coefficients a,b,c,d,e` / `--step_cache_keep FIRST,LAST` (opt-in step cache,
 `WanT2V.generate(step_cache=)`: steps whose time embedding has barely moved skip the DiT blocks and add the last computed step's
@@ -36,7 +38,7 @@ sys.path.insert(0, os.path.join(ROOT, 'moviigen1.1_amd'))
 
 import wan  # noqa: E402
 from wan.configs import SIZE_CONFIGS, SUPPORTED_SIZES, WAN_CONFIGS  # noqa: E402
-from wan.utils.utils import cache_image, cache_video, load_video, str2bool  # noqa: E402
+from wan.utils.utils import cache_image, cache_video, load_mask, load_video, str2bool  # noqa: E402
 
 EXAMPLE_PROMPT = {   # one short default per task (the reference ships long showcase prompts here)
     't2v-14B': {'prompt': 'A cat walks on the grass, realistic style.'},
@@ -79,6 +81,10 @@ FLAGS = [
                           help='video-to-video: start from this clip instead of pure noise (uint8 frames [T,H,W,3] as .npy, or any file imageio reads when it '
                                'is installed); resized to cover --size and centre-cropped. Not part of the reference CLI.')),
     ('--strength', dict(type=float, default=1.0, help='with --init_video: the fraction of the sampling schedule that runs, in (0, 1]; 1 = from pure noise.')),
+    ('--mask', dict(type=str, default=None,
+                    help='with --init_video: regenerate only where this mask is >= 128 and keep the rest of the clip (uint8 [T,H,W] or [H,W] as .npy, or any '
+                         'file --init_video accepts: the maximum of its channels); it must have the frame size of --init_video.')),
+    ('--keep_frames', dict(type=int, default=0, help='with --init_video: keep the first N frames of the clip and regenerate the rest (continuation).')),
     ('--lora', dict(type=str, action='append', default=None, metavar='PATH[:STRENGTH]',
                     help='a LoRA adapter (.safetensors: PEFT / diffusers or kohya / ComfyUI key names) merged into the DiT weights before sampling, '
                          'with an optional strength (default 1.0); may be given several times: all adapters are merged in one step, with one rounding.')),
@@ -147,6 +153,9 @@ def _validate_args(args):
     args.base_seed = args.base_seed if args.base_seed >= 0 else random.randint(0, sys.maxsize)
     assert 0.0 < args.strength <= 1.0, f'--strength must be in (0, 1], got {args.strength}'
     assert args.init_video is not None or args.strength == 1.0, '--strength needs --init_video'
+    assert args.init_video is not None or args.mask is None, '--mask needs --init_video'
+    assert args.init_video is not None or args.keep_frames == 0, '--keep_frames needs --init_video'
+    assert 0 <= args.keep_frames <= args.frame_num, f'--keep_frames must be in [0, {args.frame_num}], got {args.keep_frames}'
     args.lora = [_lora_arg(a) for a in args.lora or []]
     args.step_cache_spec = _step_cache_spec(args)
     assert args.size in SUPPORTED_SIZES[args.task], \
@@ -230,10 +239,15 @@ def generate(args):
     if args.init_video:         # every rank reads the file and encodes the clip for itself
         v2v = dict(init_video=load_video(args.init_video), strength=args.strength)
         logging.info(f"video-to-video start from {args.init_video}: {v2v['init_video'].shape[0]} frames, strength {args.strength}")
-    video = pipe.generate(prompt, size=SIZE_CONFIGS[args.size], frame_num=args.frame_num, shift=args.sample_shift,
-                          sample_solver=args.sample_solver, sampling_steps=args.sample_steps,
-                          guide_scale=args.sample_guide_scale, n_prompt=n_prompt, seed=args.base_seed,
-                          offload_model=args.offload_model, step_cache=args.step_cache_spec, **v2v)
+    run = pipe.generate
+    if args.mask or args.keep_frames:       # masked video-to-video: the same call through WanT2V.inpaint
+        v2v.update(mask=load_mask(args.mask) if args.mask else None, keep_frames=args.keep_frames)
+        run = pipe.inpaint
+        logging.info(f'inpaint: mask {args.mask}, the first {args.keep_frames} frames kept')
+    video = run(prompt, size=SIZE_CONFIGS[args.size], frame_num=args.frame_num, shift=args.sample_shift,
+                sample_solver=args.sample_solver, sampling_steps=args.sample_steps,
+                guide_scale=args.sample_guide_scale, n_prompt=n_prompt, seed=args.base_seed,
+                offload_model=args.offload_model, step_cache=args.step_cache_spec, **v2v)
     if pipe.last_step_plan is not None:
         logging.info('step cache: computed %d of %d steps: %s' % (sum(pipe.last_step_plan), len(pipe.last_step_plan),
                                                                    ''.join('C' if c else 's' for c in pipe.last_step_plan)))

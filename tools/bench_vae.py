@@ -5,7 +5,9 @@ Synthetic weights of the shipped decoder shape (dim 96), z = randn seed 7 (SURVE
 also times WanVAE.encode of a [3,81,832,1920] and a [3,81,720,1280] clip (median of --encode-reps calls, events around the whole
 call) behind the decode leg of the same run: seconds, executed TFLOP/s against the same fp32-MFMA peak, peak memory; with --stages
 the milliseconds and TFLOP/s of every encoder stage; --mode bf16x3 times the encode of a bf16x3 object; the frame ingest (mg_video_from_u8,
-1080p -> 1920x832x81) is timed behind it."""
+1080p -> 1920x832x81) is timed behind it.
+    python tools/bench_vae.py --mask
+times only the four passes of WanT2V.inpaint at 1920x832x81 (median of 5 calls each): milliseconds and GB/s."""
 import argparse
 import json
 import os
@@ -34,10 +36,63 @@ ap.add_argument('--link-gbps', type=float, default=45.0)
 ap.add_argument('--upconv', default='phases', choices=('phases', 'gather'), help="the convs behind a 2x upsample: four 2x2 phase convs / one 3x3 through the upsample")
 ap.add_argument('--encode', action='store_true', help='after the decode leg: time WanVAE.encode at 1920x832x81 and 1280x720x81 (random dim-96 encoder weights)')
 ap.add_argument('--encode-reps', type=int, default=3)
+ap.add_argument('--mask', action='store_true', help="only time the four passes of WanT2V.inpaint at 1920x832x81 (no decode, no encode): the mask's resize from "
+                                                   '1920x1080, its reduction to the latent grid, the per-step overwrite of the kept latent cells and the final composite')
 args = ap.parse_args()
 Wd, Hd = (int(v) for v in args.size.split('x'))
 T = (args.frames - 1) // 4 + 1
 dev = torch.device('cuda:0')
+
+
+def median_ms(fn, reps=5):
+    """median of `reps` timed calls behind one warm-up call, HIP events around each call"""
+    fn()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ms.append(a.elapsed_time(b))
+    return sorted(ms)[len(ms) // 2], ms
+
+
+if args.mask:
+    # masked video-to-video (WanT2V.inpaint): a rectangle mask (the inside regenerated, the kept and the regenerated halves about equal), so the
+    # overwrite and the composite touch about half of their elements.  Bytes = what a pass must move at least: every mask byte once, and for the
+    # two masked overwrites only the elements of the kept half (sources read, destination written); a 16-byte group that straddles the mask's
+    # edge also reads its destination, which is not counted.  The rate to compare with: 4.9-5.0 TB/s of the streaming kernels (DESIGN.md 3.3).
+    from wan.backend import ops
+    g = torch.Generator(device=dev).manual_seed(3)
+    mask = torch.zeros(1, 1080, 1920, dtype=torch.uint8, device=dev)
+    mask[:, 270:810, 480:1440] = 255
+    pm = torch.empty(81, 832, 1920, dtype=torch.uint8, device=dev)
+    lm = ops.mask_to_latent(ops.mask_from_u8(mask, 81, 832, 1920, out=pm), (4, 8, 8))
+    latent, z0, noise = (torch.randn(16, 21, 104, 240, device=dev, generator=g) for _ in range(3))
+    video, clip = (torch.rand(3, 81, 832, 1920, device=dev, generator=g) for _ in range(2))
+    kept_lat, kept_px = float((lm == 0).float().mean()), float((pm == 0).float().mean())
+    rows = 832                          # cover = the same width: 832 of the 1080 mask rows survive the crop
+    passes = [
+        ('mask_from_u8', '1x1080x1920 uint8 -> 81x832x1920 uint8', lambda: ops.mask_from_u8(mask, 81, 832, 1920, out=pm), rows * 1920 + pm.numel()),
+        ('mask_to_latent', '81x832x1920 uint8 -> 21x104x240 uint8', lambda: ops.mask_to_latent(pm, (4, 8, 8)), pm.numel() + lm.numel()),
+        ('masked_renoise', '[16,21,104,240] fp32, per step', lambda: ops.masked_renoise(latent, z0, noise, lm, 0.3753, 0.6247),
+         lm.numel() + int(kept_lat * latent.numel()) * 12),
+        ('mask_composite', '[3,81,832,1920] fp32, once per call', lambda: ops.mask_composite(video, clip, pm), pm.numel() + int(kept_px * video.numel()) * 8),
+    ]
+    for name, what, fn, nbytes in passes:
+        med, ms = median_ms(fn)
+        print(json.dumps({'metric': name + '_ms', 'value': med, 'all_ms': ms, 'what': what, 'bytes_min': nbytes, 'gb_per_s': nbytes / med / 1e6,
+                          'kept_fraction_latent': kept_lat, 'kept_fraction_pixels': kept_px}))
+    # the same two overwrites with everything kept: every element is read from its sources and written, the plain streaming case
+    pm.zero_()
+    lm.zero_()
+    for name, fn, nbytes in (('masked_renoise_all_kept', lambda: ops.masked_renoise(latent, z0, noise, lm, 0.3753, 0.6247), lm.numel() + latent.numel() * 12),
+                             ('mask_composite_all_kept', lambda: ops.mask_composite(video, clip, pm), pm.numel() + video.numel() * 8)):
+        med, ms = median_ms(fn)
+        print(json.dumps({'metric': name + '_ms', 'value': med, 'all_ms': ms, 'bytes_min': nbytes, 'gb_per_s': nbytes / med / 1e6}))
+    sys.exit(0)
+
 params = W.make_vae_params(96, 1)
 if args.encode:
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
