@@ -181,6 +181,10 @@ int mg_gemm_mxfp8_gelu_q(const uint8_t* Aq, int64_t lda, const uint8_t* As, int6
  *     device memory of its own and never allocates or synchronises inside a launch; a launch with a
  *     workspace is capturable in a hipGraph from its first call. */
 int64_t mg_attn_workspace_bytes(void);
+/* Queries per work item (256 or 320) of the launch mg_attn_fwd_bf16_hd128* makes for this shape on a persistent grid of n_cu workgroups
+ * (the device's CUs rounded down to a multiple of 8, minus reserve_cus rounded up to one): a pure host function, the one place that
+ * knows the item size — a launch has heads * ceil(Lq / item) items and takes tickets from 32 rounds of them per workgroup on. */
+int mg_attn_hd128_item_queries(int64_t Lq, int64_t Lk, int heads, int prescaled, int n_cu);
 int mg_attn_fwd_bf16_hd128(const uint16_t* q, int64_t ldq, const uint16_t* kp, const uint16_t* vp,
                            uint16_t* o, int64_t ldo, int64_t Lq, int64_t Lk, int heads, float scale,
                            void* workspace, void* stream);
@@ -571,7 +575,7 @@ int mg_gemm_set_variant(int variant);
 int mg_attn_set_variant(int variant);
 
 void mg_attn_w64_profile(unsigned long long* dev_buf);     /* both attention kernels: 4 waves x {fence, step A, step B, iterations} at [0, 16); the m16 kernel also stores every workgroup's {start, end} (s_memrealtime) of the last launch at [16 + 2 b]: dev_buf holds 16 + 2 x 512 + 8 entries; m16 also adds wave 0's per-item phases {first loads landed, first tile, refill wait, steady loop, drain, epilogue, items, epilogue up to its last store's issue} at [1040, 1048) */
-void mg_attn_w64_debug(int flags);                         /* bit 0: keep the pipelined result of flagged blocks (no exact pass) */
+void mg_attn_w64_debug(int flags);                         /* bit 0: keep the pipelined result of flagged blocks (no exact pass); bits 1-3: filler placement, bit 4: static partition, bits 5-6: MFMA order; bit 7: the pre-scaled entry runs FIVE query blocks per wave (320-query items) at any shape, bit 8: four at any shape */
 void mg_attn_w64_flag_counter(unsigned* dev_counter);      /* dev_counter[2]: [0] += query blocks whose pipelined pass flagged (m16: repeated with swept row maxima; w64: redone by the exact loop), [1] += m16 blocks that went on to the exact loop */
 void mg_gemm_debug_profile(unsigned long long* dev_buf);   /* GEMM variants 1/2: 8 waves x {wait+barrier, stage issue, MFMA, k-tiles} */
 void mg_gemm5_debug_profile(unsigned long long* dev_buf);  /* GEMM variants 7 / 8 / 11 / 12: per-wave s_memtime sums at [0, 64) (csrc/tools/selftest.cpp gemmprof prints each layout); variant 12 also stores every workgroup's {start, end} (s_memrealtime) at [64 + 2 b]: dev_buf holds 64 + 2 x 512 entries */

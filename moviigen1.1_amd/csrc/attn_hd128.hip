@@ -22,7 +22,7 @@
 #include "common.h"
 #include "../../include/moviigen_hip.h"
 
-#define ATT_QB 256      // queries per workgroup of both kernels
+#define ATT_QB 256      // queries per workgroup of the w64 kernel; the m16 launcher asks mg_attn_hd128_item_queries (256 or 320)
 
 // -------------------------------------------------------------------------------------------------
 // K / V -> packed tiles
@@ -73,7 +73,7 @@ int mg_attn_w64_launch(const uint16_t* q, int64_t ldq, const uint16_t* kp, const
                        int64_t Lq, int64_t Lk, int heads, float c_log2, int nqb, float* lse, hipStream_t st);
 #endif
 int mg_attn_m16_launch(const uint16_t* q, int64_t ldq, const uint16_t* kp, const uint16_t* vp, uint16_t* o, int64_t ldo,
-                       int64_t Lq, int64_t Lk, int heads, float c_log2, int prescaled, int nqb, float* lse, int reserve_cus,
+                       int64_t Lq, int64_t Lk, int heads, float c_log2, int prescaled, float* lse, int reserve_cus,
                        unsigned* workspace, hipStream_t st);
 
 // The product library has ONE head-dim-128 kernel (m16) and no switch.  The A/B library (-DMG_AB_BUILD) adds the round-2 kernel (w64, NOT the
@@ -108,16 +108,15 @@ static int attn_fwd_impl(const uint16_t* q, int64_t ldq, const uint16_t* kp, con
     if ((ldq & 7) || (ldo & 3)) return MG_ERR_SHAPE;
     if (((uintptr_t)q & 15) || ((uintptr_t)kp & 15) || ((uintptr_t)vp & 15) || ((uintptr_t)o & 7)) return MG_ERR_SHAPE;
     if (Lq == 0) return MG_OK;
-    const int64_t nqb64 = (Lq + ATT_QB - 1) / ATT_QB;
+    const int64_t nqb64 = (Lq + ATT_QB - 1) / ATT_QB;       // (the larger of the two item counts)
     if (nqb64 * heads > 0x7fffffffLL) return MG_ERR_SHAPE;
-    const int nqb = (int)nqb64;
     const float c_log2 = scale * 1.4426950408889634f;
     hipStream_t st = (hipStream_t)stream;
 #ifdef MG_AB_BUILD
     if (g_attn_variant == 3)    // the round-2 kernel knows no pre-scaled q other than "its own factor is 1"
-        return mg_attn_w64_launch(q, ldq, kp, vp, o, ldo, Lq, Lk, heads, prescaled ? 1.0f : c_log2, nqb, lse, st);
+        return mg_attn_w64_launch(q, ldq, kp, vp, o, ldo, Lq, Lk, heads, prescaled ? 1.0f : c_log2, (int)nqb64, lse, st);
 #endif
-    return mg_attn_m16_launch(q, ldq, kp, vp, o, ldo, Lq, Lk, heads, c_log2, prescaled, nqb, lse, reserve_cus, (unsigned*)workspace, st);
+    return mg_attn_m16_launch(q, ldq, kp, vp, o, ldo, Lq, Lk, heads, c_log2, prescaled, lse, reserve_cus, (unsigned*)workspace, st);
 }
 
 // bytes of the caller-owned, zero-initialised workspace of mg_attn_fwd_bf16_hd128* (one {next ticket, workgroups done} pair, padded)

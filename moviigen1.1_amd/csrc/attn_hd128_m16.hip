@@ -36,24 +36,35 @@
 // (mg_rmsnorm_rope_bf16 out_scale: the factor enters before q's one rounding to bf16), a score IS its exponent and the
 // softmax costs exp + add + half a cvt_pk per score.  SCALED = true (any q, any scale): one v_mul more per score, q is
 // used as given (no second rounding); the reference is kept in raw score units either way.
+//
+// NQ = query blocks per wave (template parameter of the kernel): 4 (64 queries per wave, 256 per item — the kernel of rounds 3-6, same
+// instructions as before it became a parameter) or 5 (80 queries per wave, 320 per item: a K or V fragment feeds five MFMAs instead of
+// four, a head's K / V stream into the CU once per 320 queries, and a tile's fixed costs spread over 160 MFMAs per wave; O^T 160 + Q 80
+// AGPRs, S^T 80 + P 40 + references 20 arch VGPRs — six blocks do not fit).  A row's arithmetic does not depend on NQ — its reference
+// comes from its first tile, its row-sum partials live in the same four lanes, its keys arrive in the same order — so an output row has
+// the same bits under both.  The RARE PATHS (rows shorter than three tiles, the true-maximum sweep with the repeated pass, the exact loop)
+// are instantiated for NQ = 5 as well: one launch, no second kernel, nothing recorded in the workspace.  Which launch gets which:
+// mg_attn_hd128_item_queries below (measured: DESIGN.md 3.1 (8)).
 #include <type_traits>
 #include "common.h"
 #include "../../include/moviigen_hip.h"
 
 #define M16_THREADS 256
-#define M16_QB 256
+// queries per workgroup: 64 * NQ (four waves of NQ query blocks of 16).  NQ = 4 is the kernel of rounds 3-6; NQ = 5 is the wider item
+// (mg_attn_hd128_item_queries is the ONE place that says which launch gets which).
 #define M16_TILE 16384
 #define M16_K(slot) ((slot) * M16_TILE)
 #define M16_V(slot) (3 * M16_TILE + (slot) * M16_TILE)
 
 MG_DEV bf16x8_t m16_bf(u32x4_t v) { return __builtin_bit_cast(bf16x8_t, v); }
+template <int NQ>
 struct M16State {
-    f32x4_t ot[8][4];      // O^T [d block][query block]             (AGPRs: builtin MFMAs)
-    f32x4_t st[2][2][4];   // S^T [unit kb][key block a/b][query block]  (arch VGPRs: inline-asm MFMAs)
-    bf16x8_t pf[2][4];     // P   [unit kb][query block]: keys 8G..8G+7 of the unit
-    f32x4_t mq[4];         // -m_ref of the lane's query in block n, four copies: C operand of an accumulator's first MFMA
-    float m_run[4], l_run[4];
-    float psa[4], psb[4];  // the pipelined pass's row-sum partials (even / odd score of a pair), folded into l_run ONCE behind the pass
+    f32x4_t ot[8][NQ];     // O^T [d block][query block]             (AGPRs: builtin MFMAs)
+    f32x4_t st[2][2][NQ];  // S^T [unit kb][key block a/b][query block]  (arch VGPRs: inline-asm MFMAs)
+    bf16x8_t pf[2][NQ];    // P   [unit kb][query block]: keys 8G..8G+7 of the unit
+    f32x4_t mq[NQ];        // -m_ref of the lane's query in block n, four copies: C operand of an accumulator's first MFMA
+    float m_run[NQ], l_run[NQ];
+    float psa[NQ], psb[NQ];  // the pipelined pass's row-sum partials (even / odd score of a pair), folded into l_run ONCE behind the pass
     int bad;
 };
 
@@ -80,10 +91,10 @@ constexpr int m16_koff(int i) { return (i >> 2) * 256 + (i & 3) * 4096; }   // K
 constexpr int m16_voff(int i) { return i * 256; }                           // V fragment i = d block
 
 // exact softmax of unit KB (true maximum of the 32 keys, rescale of O^T and l), all four query blocks
-template <int KB>
-MG_DEV void m16_softmax_exact(M16State& s, float c) {
+template <int KB, int NQ>
+MG_DEV void m16_softmax_exact(M16State<NQ>& s, float c) {
 #pragma unroll
-    for (int n = 0; n < 4; ++n) {
+    for (int n = 0; n < NQ; ++n) {
         float tmax = s.st[KB][0][n][0];
 #pragma unroll
         for (int r = 1; r < 4; ++r) tmax = fmaxf(tmax, s.st[KB][0][n][r]);
@@ -114,10 +125,10 @@ MG_DEV void m16_softmax_exact(M16State& s, float c) {
 }
 
 // softmax of unit KB whose scores are already relative to the row references (prologue): p = 2^s
-template <int KB>
-MG_DEV void m16_softmax_zero(M16State& s, float c) {
+template <int KB, int NQ>
+MG_DEV void m16_softmax_zero(M16State<NQ>& s, float c) {
 #pragma unroll
-    for (int n = 0; n < 4; ++n) {
+    for (int n = 0; n < NQ; ++n) {
         float psum = 0.f;
         float p[8];
 #pragma unroll
@@ -135,12 +146,12 @@ MG_DEV void m16_softmax_zero(M16State& s, float c) {
 
 // accumulator start of S^T for a ragged tile: -1e30 on the key rows >= lim, else `base` of the query block (0 or the
 // row reference); the MFMAs add K.Q^T to it
-template <int KB>
-MG_DEV void m16_mask_init(M16State& s, int lim, int G, const f32x4_t (&base)[4]) {
+template <int KB, int NQ>
+MG_DEV void m16_mask_init(M16State<NQ>& s, int lim, int G, const f32x4_t (&base)[NQ]) {
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk)
 #pragma unroll
-        for (int n = 0; n < 4; ++n)
+        for (int n = 0; n < NQ; ++n)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int key = KB * 32 + G * 8 + blk * 4 + r;
@@ -155,54 +166,60 @@ MG_DEV void m16_mask_init(M16State& s, int lim, int G, const f32x4_t (&base)[4])
 // two groups of this step issue them for the NEXT step from nk / nv (0 = the clamped address of this step: data unused).
 // LKO / LVO / NKO / NVO: constant byte offsets added to lds_k / lds_v / nk / nv in the reads' immediate fields — the steady loop passes the
 // SLOT's base address (a register carried across tiles) and names the unit inside the slot here: no address arithmetic per step.
-template <int KB, int SMODE, bool PV, bool SM, bool SCALED, int ORD, int LKO = 0, int LVO = 0, int NKO = 0, int NVO = 0, typename Dma>
-MG_DEV void m16_step(M16State& s, const bf16x8_t (&qf)[4][4], bf16x8_t (&kf)[4], bf16x8_t (&vf)[4], unsigned lds_k,
+template <int KB, int SMODE, bool PV, bool SM, bool SCALED, int ORD, int NQ, int LKO = 0, int LVO = 0, int NKO = 0, int NVO = 0, typename Dma>
+MG_DEV void m16_step(M16State<NQ>& s, const bf16x8_t (&qf)[NQ][4], bf16x8_t (&kf)[4], bf16x8_t (&vf)[4], unsigned lds_k,
                      unsigned lds_v, unsigned nk, unsigned nv, float c, Dma dma) {
+    static_assert(NQ == 4 || (NQ == 5 && ORD == 9), "the five-block groups exist for the shipped order only");
     constexpr int SB = 1 - KB;          // unit being exponentiated
     // (row-sum partials: s.psa / s.psb, carried through the whole pass — summed into l_run at the end of every step they were 9 VALU
     // instructions, 7 of them packed, at the bottom of each tile with the matrix pipe empty)
-    u32x4_t w[4];
+    u32x4_t w[NQ];
     float pa[2] = {0.f, 0.f}, pb[2] = {0.f, 0.f};
-    // softmax of pair pp = 2i + half (16 pairs per unit): query block n = pp >> 2, packed word pp & 3 = (key block,
-    // register pair); the pieces below are placed one by one into the eight MFMA gaps of a group
-    auto exp_a = [&](int i, int half) __attribute__((always_inline)) {
+    // softmax of pair pp (4 NQ pairs per unit; NQ = 4: pp = 2i + half, kept in slot `half`): query block n = pp >> 2, packed word
+    // pp & 3 = (key block, register pair); the pieces below are placed one by one into the MFMA gaps of a group
+    auto exp_a_p = [&](int pp, int half) __attribute__((always_inline)) {
         if (SM) {
-            const int pp = 2 * i + half, n = pp >> 2, wd = pp & 3;
+            const int n = pp >> 2, wd = pp & 3;
             const float x = s.st[SB][wd >> 1][n][(wd & 1) * 2];
             pa[half] = __builtin_amdgcn_exp2f(SCALED ? x * c : x);
             asm volatile("" : "+v"(pa[half]));     // opaque use: pins the work HERE (LLVM sinks it otherwise)
         }
     };
-    auto exp_b = [&](int i, int half) __attribute__((always_inline)) {
+    auto exp_b_p = [&](int pp, int half) __attribute__((always_inline)) {
         if (SM) {
-            const int pp = 2 * i + half, n = pp >> 2, wd = pp & 3;
+            const int n = pp >> 2, wd = pp & 3;
             const float x = s.st[SB][wd >> 1][n][(wd & 1) * 2 + 1];
             pb[half] = __builtin_amdgcn_exp2f(SCALED ? x * c : x);
             asm volatile("" : "+v"(pb[half]));
         }
     };
-    auto add_a = [&](int i, int half) __attribute__((always_inline)) {
+    auto add_a_p = [&](int pp, int half) __attribute__((always_inline)) {
         if (SM) {
-            const int n = (2 * i + half) >> 2;
+            const int n = pp >> 2;
             s.psa[n] += pa[half];
             asm volatile("" : "+v"(s.psa[n]));
         }
     };
-    auto add_b = [&](int i, int half) __attribute__((always_inline)) {
+    auto add_b_p = [&](int pp, int half) __attribute__((always_inline)) {
         if (SM) {
-            const int n = (2 * i + half) >> 2;
+            const int n = pp >> 2;
             s.psb[n] += pb[half];
             asm volatile("" : "+v"(s.psb[n]));
         }
     };
-    auto cvt = [&](int i, int half) __attribute__((always_inline)) {
+    auto cvt_p = [&](int pp, int half) __attribute__((always_inline)) {
         if (SM) {
-            const int pp = 2 * i + half, n = pp >> 2, wd = pp & 3;
+            const int n = pp >> 2, wd = pp & 3;
             unsigned pk = pack_bf2(pa[half], pb[half]);
             asm volatile("" : "+v"(pk));
             w[n][wd] = pk;
         }
     };
+    auto exp_a = [&](int i, int half) __attribute__((always_inline)) { exp_a_p(2 * i + half, half); };
+    auto exp_b = [&](int i, int half) __attribute__((always_inline)) { exp_b_p(2 * i + half, half); };
+    auto add_a = [&](int i, int half) __attribute__((always_inline)) { add_a_p(2 * i + half, half); };
+    auto add_b = [&](int i, int half) __attribute__((always_inline)) { add_b_p(2 * i + half, half); };
+    auto cvt = [&](int i, int half) __attribute__((always_inline)) { cvt_p(2 * i + half, half); };
     auto S = [&](int i, int n) __attribute__((always_inline)) {
         const int blk = i >> 2, c = i & 3, r = i & 3;
         if (SMODE == 1 && c == 0) m16_mfma_s0(s.st[KB][blk][n], kf[r], qf[n][c], s.mq[n]);
@@ -256,7 +273,58 @@ MG_DEV void m16_step(M16State& s, const bf16x8_t (&qf)[4][4], bf16x8_t (&kf)[4],
         // (profiles/r03g_attn_filler_schedule.log) — the exps want to sit together in front of a builtin MFMA.
         // ORD = where the fillers stand (a measurement parameter; the kernel launches ONE of them).  A v_exp_f32 keeps the wave's VALU for
         // four passes: in-order issue parks whatever follows a second VALU instruction of the same gap — including the next MFMA.
-        if constexpr (ORD == 0) {
+        if constexpr (NQ == 5) {
+            // Five query blocks: TEN MFMAs that share their A operand (S0..S4 P0..P4) and ten gaps.  A unit has 40 exps = 20 pairs over 8 groups:
+            // five exps per group, so every other group starts in the middle of a pair (its a-half was the previous group's last exp; the two
+            // halves of a pair sit in slot pp & 1, at most two pairs are alive).  The rules of placement 1 hold: one exp per gap, alone; [a a c]
+            // together; the fragment reads paired; nothing outside a gap.
+            //     even group:  [e][e][a a c][rK rV][e][e][a a c][e][dma][-]          odd group:  [e][a a c][e][e][a a c][rK rV][e][e][a a c][dma]
+            auto aac = [&](int pp) __attribute__((always_inline)) { add_a_p(pp, pp & 1); add_b_p(pp, pp & 1); cvt_p(pp, pp & 1); };
+            if ((i & 1) == 0) {
+                const int p0 = 5 * i / 2;
+                S(i, 0); M16_SB();
+                exp_a_p(p0, p0 & 1); M16_SB();
+                S(i, 1); M16_SB();
+                exp_b_p(p0, p0 & 1); M16_SB();
+                S(i, 2); M16_SB();
+                aac(p0); M16_SB();
+                S(i, 3); M16_SB();
+                rdK(i); M16_SB(); rdV(i); M16_SB();
+                S(i, 4); M16_SB();
+                exp_a_p(p0 + 1, (p0 + 1) & 1); M16_SB();
+                P(i, 0); M16_SB();
+                exp_b_p(p0 + 1, (p0 + 1) & 1); M16_SB();
+                P(i, 1); M16_SB();
+                aac(p0 + 1); M16_SB();
+                P(i, 2); M16_SB();
+                exp_a_p(p0 + 2, (p0 + 2) & 1); M16_SB();
+                P(i, 3); M16_SB();
+                dma(i); M16_SB();
+                P(i, 4); M16_SB();
+            } else {
+                const int p0 = (5 * i - 1) / 2;
+                S(i, 0); M16_SB();
+                exp_b_p(p0, p0 & 1); M16_SB();
+                S(i, 1); M16_SB();
+                aac(p0); M16_SB();
+                S(i, 2); M16_SB();
+                exp_a_p(p0 + 1, (p0 + 1) & 1); M16_SB();
+                S(i, 3); M16_SB();
+                exp_b_p(p0 + 1, (p0 + 1) & 1); M16_SB();
+                S(i, 4); M16_SB();
+                aac(p0 + 1); M16_SB();
+                P(i, 0); M16_SB();
+                rdK(i); M16_SB(); rdV(i); M16_SB();
+                P(i, 1); M16_SB();
+                exp_a_p(p0 + 2, (p0 + 2) & 1); M16_SB();
+                P(i, 2); M16_SB();
+                exp_b_p(p0 + 2, (p0 + 2) & 1); M16_SB();
+                P(i, 3); M16_SB();
+                aac(p0 + 2); M16_SB();
+                P(i, 4); M16_SB();
+                dma(i); M16_SB();
+            }
+        } else if constexpr (ORD == 0) {
             S(i, 0); M16_SB();
             exp_a(i, 0); exp_b(i, 0); M16_SB();
             P(i, 0); M16_SB();
@@ -395,7 +463,7 @@ MG_DEV void m16_step(M16State& s, const bf16x8_t (&qf)[4][4], bf16x8_t (&kf)[4],
 #undef M16_SB
     if (SM) {
 #pragma unroll
-        for (int n = 0; n < 4; ++n) {
+        for (int n = 0; n < NQ; ++n) {
             s.pf[SB][n] = m16_bf(w[n]);
         }
     }
@@ -415,7 +483,7 @@ struct M16NoDma {
     __device__ __forceinline__ void operator()(int) const {}
 };
 
-template <bool PROF, bool SCALED, int ORD>
+template <bool PROF, bool SCALED, int ORD, int NQ>
 __global__ __launch_bounds__(M16_THREADS, 1) void attn_hd128_m16_kernel(
     const uint16_t* __restrict__ q, int64_t ldq, const uint16_t* __restrict__ kp, const uint16_t* __restrict__ vp,
     uint16_t* __restrict__ o, int64_t ldo, int64_t Lq, int64_t Lk, int heads, float c_log2, int nqb, int dbg,
@@ -455,11 +523,11 @@ __global__ __launch_bounds__(M16_THREADS, 1) void attn_hd128_m16_kernel(
     __syncthreads();                    // the previous item's last LDS reads are done before this one's DMA
     if (PROF) ph_t = __builtin_amdgcn_s_memtime();
 
-    // Q fragments (B operand): query block n of this wave = rows 64*wave + 16*n + qi, d = 32*c + 8*G .. +7
-    bf16x8_t qf[4][4];
-    const int64_t qrow_base = (int64_t)qb0 * M16_QB + wave * 64 + qi;
+    // Q fragments (B operand): query block n of this wave = rows 16*NQ*wave + 16*n + qi, d = 32*c + 8*G .. +7
+    bf16x8_t qf[NQ][4];
+    const int64_t qrow_base = (int64_t)qb0 * (64 * NQ) + wave * (16 * NQ) + qi;
 #pragma unroll
-    for (int n = 0; n < 4; ++n) {
+    for (int n = 0; n < NQ; ++n) {
         const int64_t qr = qrow_base + n * 16;
         const int64_t qrow = qr < Lq ? qr : Lq - 1;
         const uint16_t* qp = q + qrow * ldq + head * 128 + G * 8;
@@ -500,15 +568,15 @@ __global__ __launch_bounds__(M16_THREADS, 1) void attn_hd128_m16_kernel(
     auto k_addr = [&](int slot, int kb) __attribute__((always_inline)) { return kbase + slot * M16_TILE + kb * 512; };
     auto v_addr = [&](int slot, int kb) __attribute__((always_inline)) { return vbase + slot * M16_TILE + kb * 8192; };
 
-    M16State s;
+    M16State<NQ> s;
     bf16x8_t kf[4], vf[4];
     auto reset = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int d = 0; d < 8; ++d)
 #pragma unroll
-            for (int n = 0; n < 4; ++n) s.ot[d][n] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+            for (int n = 0; n < NQ; ++n) s.ot[d][n] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int n = 0; n < 4; ++n) s.m_run[n] = -1e30f, s.l_run[n] = 0.f, s.psa[n] = 0.f, s.psb[n] = 0.f;
+        for (int n = 0; n < NQ; ++n) s.m_run[n] = -1e30f, s.l_run[n] = 0.f, s.psa[n] = 0.f, s.psb[n] = 0.f;
         s.bad = 0;
     };
     reset();
@@ -519,7 +587,7 @@ __global__ __launch_bounds__(M16_THREADS, 1) void attn_hd128_m16_kernel(
     // here, the wave waited for its 16 Q loads before it asked for the tiles — two memory round trips in a row at the start of every item.
     auto q_pin = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int n = 0; n < 4; ++n)
+        for (int n = 0; n < NQ; ++n)
 #pragma unroll
             for (int c = 0; c < 4; ++c) asm volatile("" : "+a"(qf[n][c]));
     };
@@ -538,7 +606,7 @@ __global__ __launch_bounds__(M16_THREADS, 1) void attn_hd128_m16_kernel(
         m16_rd<m16_koff(1)>(kf[1], ak);
         m16_rd<m16_voff(1)>(vf[1], av);
     };
-    const f32x4_t zero4[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    const f32x4_t zero4[NQ] = {};
     // bare S^T of one unit (prologue / reference sweep / exact loop): 32 MFMAs, plain loads, RAW scores
     auto bare_S = [&](auto kbc, int slot, int lim) __attribute__((always_inline)) {
         constexpr int KB = decltype(kbc)::value;
@@ -547,14 +615,14 @@ __global__ __launch_bounds__(M16_THREADS, 1) void attn_hd128_m16_kernel(
 #pragma unroll
             for (int blk = 0; blk < 2; ++blk)
 #pragma unroll
-                for (int n = 0; n < 4; ++n) s.st[KB][blk][n] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+                for (int n = 0; n < NQ; ++n) s.st[KB][blk][n] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
         }
         const char* base = smem + M16_K(slot) + G * 1024 + qi * 16 + KB * 512;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const bf16x8_t f = *(const bf16x8_t*)(base + m16_koff(i));
 #pragma unroll
-            for (int n = 0; n < 4; ++n)
+            for (int n = 0; n < NQ; ++n)
                 s.st[KB][i >> 2][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f, qf[n][i & 3], s.st[KB][i >> 2][n], 0, 0, 0);
         }
     };
@@ -565,7 +633,7 @@ __global__ __launch_bounds__(M16_THREADS, 1) void attn_hd128_m16_kernel(
         for (int i = 0; i < 8; ++i) {
             const bf16x8_t f = *(const bf16x8_t*)(base + m16_voff(i));
 #pragma unroll
-            for (int n = 0; n < 4; ++n)
+            for (int n = 0; n < NQ; ++n)
                 s.ot[i][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f, s.pf[KB][n], s.ot[i][n], 0, 0, 0);
         }
     };
@@ -576,9 +644,9 @@ __global__ __launch_bounds__(M16_THREADS, 1) void attn_hd128_m16_kernel(
     if (!exact_pass) {
     for (int attempt = 0;; ++attempt) {
         // per-row maximum of the RAW scores in s.st[0..1] (the 64 keys of one tile), folded into mx
-        auto tile_max = [&](float (&mx)[4]) __attribute__((always_inline)) {
+        auto tile_max = [&](float (&mx)[NQ]) __attribute__((always_inline)) {
 #pragma unroll
-            for (int n = 0; n < 4; ++n) {
+            for (int n = 0; n < NQ; ++n) {
                 float a = fmaxf(fmaxf(s.st[0][0][n][0], s.st[0][0][n][1]), fmaxf(s.st[0][0][n][2], s.st[0][0][n][3]));
                 float b = fmaxf(fmaxf(s.st[0][1][n][0], s.st[0][1][n][1]), fmaxf(s.st[0][1][n][2], s.st[0][1][n][3]));
                 float c2 = fmaxf(fmaxf(s.st[1][0][n][0], s.st[1][0][n][1]), fmaxf(s.st[1][0][n][2], s.st[1][0][n][3]));
@@ -586,9 +654,9 @@ __global__ __launch_bounds__(M16_THREADS, 1) void attn_hd128_m16_kernel(
                 mx[n] = fmaxf(mx[n], fmaxf(fmaxf(a, b), fmaxf(c2, d2)));
             }
         };
-        auto set_reference = [&](const float (&mx)[4], float above) __attribute__((always_inline)) {
+        auto set_reference = [&](const float (&mx)[NQ], float above) __attribute__((always_inline)) {
 #pragma unroll
-            for (int n = 0; n < 4; ++n) {       // a query's keys are spread over the four G lanes
+            for (int n = 0; n < NQ; ++n) {       // a query's keys are spread over the four G lanes
                 float m = fmaxf(mx[n], __shfl_xor(mx[n], 16, 64));
                 m = fmaxf(m, __shfl_xor(m, 32, 64)) + above;
                 s.mq[n] = (f32x4_t){-m, -m, -m, -m};
@@ -599,7 +667,8 @@ __global__ __launch_bounds__(M16_THREADS, 1) void attn_hd128_m16_kernel(
             // reference sweep (only after a flagged pass): TRUE row maxima.  S^T of every tile (64 MFMAs
             // per wave and tile), one barrier per tile, no V, no exponentials.
             // ------------------------------------------------------------------------------------------
-            float mx[4] = {-1e30f, -1e30f, -1e30f, -1e30f};
+            float mx[NQ] = {-1e30f, -1e30f, -1e30f, -1e30f};       // (a loop here changes the register allocation of the whole kernel)
+            if constexpr (NQ == 5) mx[4] = -1e30f;
             // K tiles ride a ring of all six 16 KiB slots, four tiles ahead (tile t in slot t % 6; indices past the end
             // are clamped: a redundant reload into a slot nobody reads), so a tile's DMA latency is covered by the S^T of
             // three others; vmcnt(12) = this wave's pieces of the OLDEST of the four tiles in flight have landed
@@ -636,7 +705,8 @@ __global__ __launch_bounds__(M16_THREADS, 1) void attn_hd128_m16_kernel(
             // tile 0's, so the largest term of a row is at least 2^-64 (every term that matters stays a normal fp32 /
             // bf16 number) and the headroom above grows to 2^(90+64): the pass is good for rows whose best key beats
             // the best of the first 64 by up to 154 bits = 106 natural units
-            float mx[4] = {-1e30f, -1e30f, -1e30f, -1e30f};
+            float mx[NQ] = {-1e30f, -1e30f, -1e30f, -1e30f};       // (a loop here changes the register allocation of the whole kernel)
+            if constexpr (NQ == 5) mx[4] = -1e30f;
             tile_max(mx);
             set_reference(mx, c_log2 > 1e-20f ? 64.f / c_log2 : 0.f);       // (raw score units: an exponent is score * c)
         }
@@ -645,14 +715,14 @@ __global__ __launch_bounds__(M16_THREADS, 1) void attn_hd128_m16_kernel(
 #pragma unroll
             for (int blk = 0; blk < 2; ++blk)
 #pragma unroll
-                for (int n = 0; n < 4; ++n) s.st[kb][blk][n] += s.mq[n];
+                for (int n = 0; n < NQ; ++n) s.st[kb][blk][n] += s.mq[n];
         m16_softmax_zero<0>(s, c_log2);
 #pragma unroll
-        for (int n = 0; n < 4; ++n) asm volatile("" : "+v"(s.l_run[n]));     // summed HERE: left alone, the compiler sinks these 32 adds behind the steady loop (their
+        for (int n = 0; n < NQ; ++n) asm volatile("" : "+v"(s.l_run[n]));     // summed HERE: left alone, the compiler sinks these 32 adds behind the steady loop (their
         //                                                                      first use) and carries the 32 addends across it — through scratch
         // step u = 1: S(1,0) | P.V(0,0) | softmax S(0,1)
         prefetch(k_addr(1, 0), v_addr(0, 0));
-        m16_step<0, 1, true, true, SCALED, ORD>(s, qf, kf, vf, k_addr(1, 0), v_addr(0, 0), k_addr(1, 1), v_addr(0, 1), c_log2, M16NoDma());
+        m16_step<0, 1, true, true, SCALED, ORD, NQ>(s, qf, kf, vf, k_addr(1, 0), v_addr(0, 0), k_addr(1, 1), v_addr(0, 1), c_log2, M16NoDma());
         int t = 1;
         // ---- steady loop, with its state CARRIED instead of recomputed (round 5).  Per tile the loop used to spend ~35 instructions outside
         // MFMA gaps — slot indices -> eight LDS read addresses, two 64-bit global addresses with their clamps, M0 values — clumped at the top of
@@ -689,7 +759,7 @@ __global__ __launch_bounds__(M16_THREADS, 1) void attn_hd128_m16_kernel(
             fence_hot();                // K(t+1), V(t) visible; everyone is past iteration t-1
             const unsigned long long c1 = PROF ? __builtin_amdgcn_s_memtime() : 0;
             // u = 2t: S(t,1) [K slot of t] | P.V(t-1,1) [V slot of t-1] | softmax S(t,0); refill K(t+2) -> slot of t-1, V(t+1) -> slot of t+1
-            m16_step<1, 1, true, true, SCALED, ORD, 512, 8192, 0, 0>(s, qf, kf, vf, ka1, va0, ka2, va1, c_log2,
+            m16_step<1, 1, true, true, SCALED, ORD, NQ, 512, 8192, 0, 0>(s, qf, kf, vf, ka1, va0, ka2, va1, c_log2,
                                        [&](int n) __attribute__((always_inline)) {   // all 8 refill pieces here (step B gives them time to land)
                                            switch (n) {
                                                case 0: M16_BDMA0(dvo, rs_k, offk, lk0, 0); break;       // M0 once per operand: the pieces'
@@ -704,7 +774,7 @@ __global__ __launch_bounds__(M16_THREADS, 1) void attn_hd128_m16_kernel(
                                        });
             const unsigned long long c2 = PROF ? __builtin_amdgcn_s_memtime() : 0;
             // u = 2t+1: S(t+1,0) [K slot of t+1] | P.V(t,0) [V slot of t] | softmax S(t,1); in its free gaps the state steps to tile t+1
-            m16_step<0, 1, true, true, SCALED, ORD, 0, 0, 512, 8192>(s, qf, kf, vf, ka2, va1, ka2, va1, c_log2,
+            m16_step<0, 1, true, true, SCALED, ORD, NQ, 0, 0, 512, 8192>(s, qf, kf, vf, ka2, va1, ka2, va1, c_log2,
                                        [&](int n) __attribute__((always_inline)) {
                                            if (n == 0)
                                                asm volatile("s_add_u32 %0, %0, 0x4000\n\ts_add_u32 %1, %1, 0x4000" : "+s"(offk), "+s"(offv) : : "scc");
@@ -738,30 +808,30 @@ __global__ __launch_bounds__(M16_THREADS, 1) void attn_hd128_m16_kernel(
         if (t + 1 < T) {                // a ragged tile t+1 follows: its V is staged now (slot s2)
             dma_v4(t + 1, s2);
         }
-        m16_step<1, 1, true, true, SCALED, ORD>(s, qf, kf, vf, k_addr(s1, 1), v_addr(s0, 1), k_addr(s2, 0), v_addr(s1, 0), c_log2, M16NoDma());
+        m16_step<1, 1, true, true, SCALED, ORD, NQ>(s, qf, kf, vf, k_addr(s1, 1), v_addr(s0, 1), k_addr(s2, 0), v_addr(s1, 0), c_log2, M16NoDma());
         if (t + 1 < T) {
             // u = 2t+1 with the masked start for S(t+1,0)
             m16_mask_init<0>(s, last_lim, G, s.mq);
-            m16_step<0, 2, true, true, SCALED, ORD>(s, qf, kf, vf, k_addr(s2, 0), v_addr(s1, 0), k_addr(s2, 1), v_addr(s1, 1), c_log2, M16NoDma());
+            m16_step<0, 2, true, true, SCALED, ORD, NQ>(s, qf, kf, vf, k_addr(s2, 0), v_addr(s1, 0), k_addr(s2, 1), v_addr(s1, 1), c_log2, M16NoDma());
             fence();                    // V(t+1) landed
             // u = 2t+2: S(t+1,1) masked | P.V(t,1) | softmax S(t+1,0)
             m16_mask_init<1>(s, last_lim, G, s.mq);
-            m16_step<1, 2, true, true, SCALED, ORD>(s, qf, kf, vf, k_addr(s2, 1), v_addr(s1, 1), k_addr(s2, 1), v_addr(s2, 0), c_log2, M16NoDma());
+            m16_step<1, 2, true, true, SCALED, ORD, NQ>(s, qf, kf, vf, k_addr(s2, 1), v_addr(s1, 1), k_addr(s2, 1), v_addr(s2, 0), c_log2, M16NoDma());
             // u = 2t+3: P.V(t+1,0) | softmax S(t+1,1)
-            m16_step<0, 0, true, true, SCALED, ORD>(s, qf, kf, vf, k_addr(s2, 1), v_addr(s2, 0), k_addr(s2, 1), v_addr(s2, 1), c_log2, M16NoDma());
+            m16_step<0, 0, true, true, SCALED, ORD, NQ>(s, qf, kf, vf, k_addr(s2, 1), v_addr(s2, 0), k_addr(s2, 1), v_addr(s2, 1), c_log2, M16NoDma());
             // u = 2t+4: P.V(t+1,1)
-            m16_step<1, 0, true, false, SCALED, ORD>(s, qf, kf, vf, k_addr(s2, 1), v_addr(s2, 1), k_addr(s2, 1), v_addr(s2, 1), c_log2, M16NoDma());
+            m16_step<1, 0, true, false, SCALED, ORD, NQ>(s, qf, kf, vf, k_addr(s2, 1), v_addr(s2, 1), k_addr(s2, 1), v_addr(s2, 1), c_log2, M16NoDma());
         } else {
             // u = 2t+1: P.V(t,0) | softmax S(t,1)
-            m16_step<0, 0, true, true, SCALED, ORD>(s, qf, kf, vf, k_addr(s1, 1), v_addr(s1, 0), k_addr(s1, 1), v_addr(s1, 1), c_log2, M16NoDma());
+            m16_step<0, 0, true, true, SCALED, ORD, NQ>(s, qf, kf, vf, k_addr(s1, 1), v_addr(s1, 0), k_addr(s1, 1), v_addr(s1, 1), c_log2, M16NoDma());
             // u = 2t+2: P.V(t,1)
-            m16_step<1, 0, true, false, SCALED, ORD>(s, qf, kf, vf, k_addr(s1, 1), v_addr(s1, 1), k_addr(s1, 1), v_addr(s1, 1), c_log2, M16NoDma());
+            m16_step<1, 0, true, false, SCALED, ORD, NQ>(s, qf, kf, vf, k_addr(s1, 1), v_addr(s1, 1), k_addr(s1, 1), v_addr(s1, 1), c_log2, M16NoDma());
         }
         m16_wait<0>();
         // the last prefetches of the chain are never consumed: keep the ring alive until they have landed
         asm volatile("" ::"v"(kf[0]), "v"(kf[1]), "v"(kf[2]), "v"(kf[3]), "v"(vf[0]), "v"(vf[1]), "v"(vf[2]), "v"(vf[3]));
 #pragma unroll
-        for (int n = 0; n < 4; ++n) {       // ONE range test of the final row sums (2^-64 .. 2^90 expected; inf / NaN fail too)
+        for (int n = 0; n < NQ; ++n) {       // ONE range test of the final row sums (2^-64 .. 2^90 expected; inf / NaN fail too)
             s.l_run[n] += s.psa[n] + s.psb[n];      // (l only grows, inf / NaN are sticky)
             s.psa[n] = s.psb[n] = 0.f;
             float lt = s.l_run[n] + __shfl_xor(s.l_run[n], 16, 64);
@@ -804,11 +874,11 @@ __global__ __launch_bounds__(M16_THREADS, 1) void attn_hd128_m16_kernel(
         qi = l3 & 15, G = l3 >> 4;
     }
 #pragma unroll
-    for (int n = 0; n < 4; ++n) {
+    for (int n = 0; n < NQ; ++n) {
         float l_tot = s.l_run[n] + __shfl_xor(s.l_run[n], 16, 64);
         l_tot += __shfl_xor(l_tot, 32, 64);
         const float inv = 1.f / l_tot;
-        const int64_t qr = (int64_t)qb0 * M16_QB + wave * 64 + n * 16 + qi;
+        const int64_t qr = (int64_t)qb0 * (64 * NQ) + wave * (16 * NQ) + n * 16 + qi;
         if (lse && G == 0 && qr < Lq) lse[(int64_t)head * Lq + qr] = (s.m_run[n] * c_log2 + __log2f(l_tot)) * 0.6931471805599453f;
         if (qr < Lq) {
             uint16_t* op = o + qr * ldo + head * 128 + G * 4;
@@ -862,11 +932,47 @@ void mg_attn_m16_hooks(int dbg, unsigned long long* prof, unsigned* flagcnt) { g
 // the XCDs, so 8 = one CU per XCD).  A persistent workgroup owns its CU's whole register file for the length of the
 // launch: a kernel on another stream — RCCL's all-to-all of the next head group (wan/distributed/ulysses.py) — can only
 // run on CUs this grid does not occupy.
+// THE item size: queries per workgroup item of a launch, 256 (NQ = 4) or 320 (NQ = 5).  Everything that counts items — this launcher, the
+// ticket threshold, wan.backend.ops.attention_item_queries (HeadExchange's round report), the selftest — asks here.
+// The rule is what the same-operand A/B runs say (profiles/r07a_attn_nq5_ab.log, profiles/r07a_attn_nq5_threshold.log): a 320-query item
+// costs 3.7 ... 4.3 % less per query than a 256-query item, and a launch gains or loses by how its items fall into ROUNDS over the
+// persistent grid — 131 040 x 40 heads (tickets, 80 -> 64.06 rounds) +2.7 %, x 8 heads (16 -> 13 rounds) +2.2 %, 65 520 x 16 heads +2.0 %;
+// x 10 heads (20 -> 17 rounds = 21.25 of the old) -2.2 %, x 5 heads (10 -> 9) -7.7 %, 32 760 x 40 heads (20 -> 17) -3.6 %.  So: five blocks when
+// the launch's cost in (rounds x queries per item), priced 3 % lower, is below the four-block launch's; only for the pre-scaled entry (what the
+// DiT's self-attention calls), from 6 rounds of 256-query items on (the smallest launch measured) and from 65 520 keys on (the shortest key range
+// measured; below it every launch runs the kernel of rounds 3-6).  (A launch of >= 32 rounds is priced as ticketed whether or not the caller
+// gave a workspace: without one its static partition loses at most one round in 32.)
+static double m16_launch_cost(int64_t items, int n_cu, int item_q) {
+    if (items <= n_cu) return item_q;
+    if (items >= 32 * (int64_t)n_cu) return (double)items / n_cu * item_q;      // tickets: no round quantisation, the tail is part of the measured 3 %
+    const int64_t per = n_cu >= 8 ? n_cu / 8 : 1;
+    int64_t rounds = 0;
+    for (int x = 0; x < 8; ++x) {       // the static partition of the kernel's work loop: XCD x owns items [x, x + 1) * total / 8
+        const int64_t r = ((x + 1) * items / 8 - x * items / 8 + per - 1) / per;
+        rounds = r > rounds ? r : rounds;
+    }
+    return (double)rounds * item_q;
+}
+extern "C" int mg_attn_hd128_item_queries(int64_t Lq, int64_t Lk, int heads, int prescaled, int n_cu) {
+    if (!prescaled || n_cu < 8 || heads <= 0 || Lq <= 0 || Lk < 65520) return 256;
+    const int64_t items4 = (Lq + 255) / 256 * heads, items5 = (Lq + 319) / 320 * heads;
+    if (items4 < 6 * (int64_t)n_cu) return 256;
+    return 0.97 * m16_launch_cost(items5, n_cu, 320) < m16_launch_cost(items4, n_cu, 256) ? 320 : 256;
+}
+
 int mg_attn_m16_launch(const uint16_t* q, int64_t ldq, const uint16_t* kp, const uint16_t* vp, uint16_t* o, int64_t ldo,
-                       int64_t Lq, int64_t Lk, int heads, float c_log2, int prescaled, int nqb, float* lse, int reserve_cus,
+                       int64_t Lq, int64_t Lk, int heads, float c_log2, int prescaled, float* lse, int reserve_cus,
                        unsigned* workspace, hipStream_t st) {
     const int n_cu = mg_persistent_cus(reserve_cus);    // one workgroup per CU (96 KiB LDS), a multiple of the 8 XCDs
     if (n_cu < 0) return MG_ERR_LAUNCH;
+    int item_q = mg_attn_hd128_item_queries(Lq, Lk, heads, prescaled, n_cu);
+#ifdef MG_AB_BUILD
+    if ((g_m16_dbg & 128) && prescaled) item_q = 320;      // measurement: debug bit 7 forces five query blocks at any shape, bit 8 four
+    if (g_m16_dbg & 256) item_q = 256;
+#endif
+    const int64_t nqb64 = (Lq + item_q - 1) / item_q;
+    if (nqb64 * heads > 0x7fffffffLL) return MG_ERR_SHAPE;
+    const int nqb = (int)nqb64;
     const int total = nqb * heads;
     const unsigned grid = total <= n_cu ? (unsigned)total : (unsigned)n_cu;   // persistent when there is more work than CUs
     // Items by ticket from 32 rounds on (the metric's launch has 80: +1.35 %, 220.3 against 223.3 ms; 16 rounds: -0.2 %, and at the 10 rounds of
@@ -876,9 +982,15 @@ int mg_attn_m16_launch(const uint16_t* q, int64_t ldq, const uint16_t* kp, const
         tickets = workspace;
 #define M16_ORD 9      // what the library ships (m16_step): one v_exp_f32 per MFMA gap, alone (placement 1, profiles/r05m_attn_order.log: +4.8 % over placement 0), and
                        // the MFMAs of a group in quads that share their A operand (profiles/r06s_attn_mfma_order.log: +0.3 ... +0.5 % over S P S P, same cycles, same bits)
-#define M16_LAUNCH(PROF, SCALED, ORD)                                                                                             \
-    hipLaunchKernelGGL((attn_hd128_m16_kernel<PROF, SCALED, ORD>), dim3(grid), dim3(M16_THREADS), 0, st, q, ldq, kp, vp, o, ldo, Lq, \
+#define M16_LAUNCH_NQ(PROF, SCALED, ORD, NQ)                                                                                      \
+    hipLaunchKernelGGL((attn_hd128_m16_kernel<PROF, SCALED, ORD, NQ>), dim3(grid), dim3(M16_THREADS), 0, st, q, ldq, kp, vp, o, ldo, Lq, \
                        Lk, heads, prescaled ? 1.0f : c_log2, nqb, g_m16_dbg, PROF ? g_m16_prof : nullptr, lse, g_m16_flagcnt, tickets)
+#define M16_LAUNCH(PROF, SCALED, ORD) M16_LAUNCH_NQ(PROF, SCALED, ORD, 4)
+    if (item_q == 320) {        // (mg_attn_hd128_item_queries: the pre-scaled entry only)
+        if (g_m16_prof) M16_LAUNCH_NQ(true, false, M16_ORD, 5);
+        else M16_LAUNCH_NQ(false, false, M16_ORD, 5);
+        return mg_check_launch();
+    }
 #ifdef MG_AB_BUILD
     const int ord = (g_m16_dbg >> 1) & 7;     // measurement: mg_attn_w64_debug(2 * k) runs the pre-scaled entry on placement k
     const int mo = (g_m16_dbg >> 5) & 3;      // measurement: debug bits 5-6 = MFMA order of a group (1: pairs, 2: quads sharing their A operand) under placement 1's gaps
@@ -906,5 +1018,6 @@ int mg_attn_m16_launch(const uint16_t* q, int64_t ldq, const uint16_t* kp, const
         else M16_LAUNCH(false, true, M16_ORD);
     }
 #undef M16_LAUNCH
+#undef M16_LAUNCH_NQ
     return mg_check_launch();
 }

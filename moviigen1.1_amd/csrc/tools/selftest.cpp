@@ -477,7 +477,7 @@ static void attn_ab(int64_t L, int heads, int data, const std::vector<int>& vari
     for (int r = 0; r < rounds; ++r)
         for (int var : variants) {
             // variant: 0 = m16 general entry, 3 = w64; 10 + k = m16 through the pre-scaled entry with debug flags 2*k
-            // (k = 1: the alternative filler schedule)
+            // (k = 1: the alternative filler schedule; 74 = 10 + 64: debug bit 7 = five query blocks per wave at any shape, 138: bit 8 = four)
             mg_attn_set_variant(var >= 10 ? 0 : var);
             mg_attn_w64_debug(var >= 10 ? 2 * (var - 10) : 0);
             rc = mg_pack_kv_bf16(dk.p, ld, dv.p, ld, L, heads, 128, dkp.p, dvp.p, 0);   // the K row order follows the kernel
@@ -494,13 +494,18 @@ static void attn_ab(int64_t L, int heads, int data, const std::vector<int>& vari
             auto got = dout.host();
             double err = rc ? 1e9 : 0;
             const int pre = var >= 10;
+            hipDeviceProp_t prop;
+            CK(hipGetDeviceProperties(&prop, 0));
+            const int dbg = var >= 10 ? 2 * (var - 10) : 0;       // the item size of this launch: forced, else the launcher's rule
+            const int item_q = var == 3 || (dbg & 256) ? 256 : (dbg & 128) ? 320
+                               : mg_attn_hd128_item_queries(L, L, heads, pre, (prop.multiProcessorCount & ~7) - ((reserve + 7) & ~7));
             for (int it = 0; it < nsamp; ++it)
                 for (int d = 0; d < 128; ++d)
                     err = fmax(err, fabs(bf2f(got[(size_t)sq[it] * ld + sh[it] * 128 + d]) - ref[pre][it][d]));
             const bool ok = err <= 2e-2 * fmax(ref_max[pre], 1e-3);
             if (!ok) ++n_fail;
             printf("  [%s] variant %d round %d: %.3f ms  %.1f TFLOP/s  flagged blocks %u (exact loop %u) of %lld  max_err %.3e (ref max %.3e)\n",
-                   ok ? "PASS" : "FAIL", var, r, ms, flop / (ms * 1e-3) / 1e12, flagged, to_exact, (long long)((L + 255) / 256) * heads, err, ref_max[pre]);
+                   ok ? "PASS" : "FAIL", var, r, ms, flop / (ms * 1e-3) / 1e12, flagged, to_exact, (long long)((L + item_q - 1) / item_q) * heads, err, ref_max[pre]);
             fflush(stdout);
         }
     mg_attn_w64_flag_counter(nullptr);

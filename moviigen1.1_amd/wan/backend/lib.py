@@ -36,6 +36,7 @@ SIGNATURES = {
     'mg_gemm_mxfp8_gelu_q': [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_i64,
                              c_vp],
     'mg_attn_workspace_bytes': [],
+    'mg_attn_hd128_item_queries': [c_i64, c_i64, c_int, c_int, c_int],
     'mg_attn_fwd_bf16_hd128': [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_f32, c_vp, c_vp],
     'mg_attn_fwd_bf16_hd128_lse': [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_f32, c_vp, c_vp],
     'mg_attn_fwd_bf16_hd128_prescaled': [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp],

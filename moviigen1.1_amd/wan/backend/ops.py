@@ -210,6 +210,12 @@ def attention_workspace(device=None, stream=None):
     return ws
 
 
+def attention_item_queries(lq, lk, heads, prescaled=True, n_cu=256):
+    """queries per work item (256 or 320) of the attention_hd128 launch for this shape on a persistent grid of n_cu workgroups: the library's
+    own rule (mg_attn_hd128_item_queries, a host function — no GPU needed).  A launch has heads * ceil(lq / item) items."""
+    return int(lib.load().mg_attn_hd128_item_queries(int(lq), int(lk), int(heads), int(bool(prescaled)), int(n_cu)))
+
+
 def attention_hd128(q, kp, vp, out, lk, heads, scale, prescaled=False, reserve_cus=0, workspace='stream', lse=None):
     """q [Lq, >=heads*128] bf16; kp/vp from pack_kv for the same lk keys; out [Lq, >=heads*128].
     prescaled: q was produced with rmsnorm_rope(out_scale=scale * ATTN_LOG2E) — `scale` is then only documentation.

@@ -54,9 +54,12 @@ def split_heads(n_loc, max_groups):
 
 
 def attention_rounds(n_heads, L, n_cu=256, qblock=256):
-    """rounds ONE launch of the persistent head-dim-128 kernel takes for `n_heads` heads over L queries: heads x ceil(L / 256) items of
-    one 256-query block each, dealt to the 8 XCDs in contiguous ranges and walked by the n_cu / 8 workgroups of an XCD in rounds
-    (csrc/attn_hd128_m16.hip: the work loop).  A round lasts as long as one item whatever the number of busy workgroups."""
+    """rounds ONE launch of the persistent head-dim-128 kernel takes for `n_heads` heads over L queries: heads x ceil(L / qblock) items of
+    one qblock-query block each, dealt to the 8 XCDs in contiguous ranges and walked by the n_cu / 8 workgroups of an XCD in rounds
+    (csrc/attn_hd128_m16.hip: the work loop).  A round lasts as long as one item whatever the number of busy workgroups.
+    qblock: 256, or None = what the library's launcher picks for this self-attention shape (ops.attention_item_queries: 256 or 320)."""
+    if qblock is None:
+        qblock = ops.attention_item_queries(L, L, n_heads, True, n_cu)
     items = n_heads * ((L + qblock - 1) // qblock)
     per_xcd_wg = max(1, (n_cu & ~7) // 8)
     if items <= (n_cu & ~7):
@@ -67,7 +70,7 @@ def attention_rounds(n_heads, L, n_cu=256, qblock=256):
 def choose_groups(n_loc, L, P, dim=None, max_groups=5, n_cu=256, tflops_per_cu=5.8, link_gbps=45.0):
     """How many pipeline groups the rank's n_loc heads are cut into (a fixed 5 ignored the round quantisation of
     the persistent attention grid — five 2-head groups of configs[3] take 6 rounds per launch for 5.08 rounds of work, -15 %).
-    Cost of a layer with G groups = sum over the groups of attention_rounds(n_g) x (time of one 256-query item over L keys)
+    Cost of a layer with G groups = sum over the groups of attention_rounds(n_g) x (time of one item over L keys: 256 or 320 queries, the launcher's rule)
                                    + the part of the exchange no attention can hide: the first group's q|k|v exchange and the last group's
                                      return = 1 / G of the layer's exchange (4 * (L / P) * dim * 2 bytes / P per link);
     the smallest cost wins, ties go to MORE groups.  With the exchange term small this is "fewest rounds, then most groups".
@@ -78,8 +81,11 @@ def choose_groups(n_loc, L, P, dim=None, max_groups=5, n_cu=256, tflops_per_cu=5
     t_exch = 4.0 * (L / P) * dim * 2 / P / (link_gbps * 1e9) * 1e3 if P > 1 else 0.0   # ms per layer on one link (all links concurrent)
     best = None
     for G in range(1, max(1, min(int(n_loc), int(max_groups))) + 1):
-        rounds = sum(attention_rounds(n, L, n_cu) for _, n in split_heads(n_loc, G))
-        cost = rounds * t_item + t_exch / G
+        rounds, cost = 0, t_exch / G
+        for _, n in split_heads(n_loc, G):
+            qb = ops.attention_item_queries(L, L, n, True, n_cu)       # 256- or 320-query items: the launcher's rule
+            r = attention_rounds(n, L, n_cu, qb)
+            rounds, cost = rounds + r, cost + r * t_item * qb / 256
         if best is None or cost < best[2] - 1e-9 or (abs(cost - best[2]) <= 1e-9 and G > best[0]):
             best = (G, rounds, cost)
     return best
@@ -152,7 +158,7 @@ class HeadExchange:
         # exchange it could hide (512 query blocks of a one-head group on 248 instead of 256 workgroups = three rounds
         # instead of two: +28 % attention time) — the default is 0; the copy-engine transport needs none either way.
         self.reserve_cus = 0 if self.peer is not None or len(self.groups) < 2 else int(os.environ.get('MOVIIGEN_SP_RESERVE_CUS', '0') or 0)
-        self.rounds = sum(attention_rounds(n, P * Lloc, (n_cu & ~7) - ((self.reserve_cus + 7) & ~7)) for _, n in self.groups)
+        self.rounds = sum(attention_rounds(n, P * Lloc, (n_cu & ~7) - ((self.reserve_cus + 7) & ~7), None if head_dim == 128 else 256) for _, n in self.groups)
         ev = lambda: [torch.cuda.Event() for _ in self.groups]  # noqa: E731
         self.ev_pack, self.ev_recv, self.ev_attn, self.ev_o = ev(), ev(), ev(), ev()
 

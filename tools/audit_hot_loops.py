@@ -31,7 +31,10 @@ KERNELS = [
     ('gemm_bf16_v12.hip', 'gemm_bf16_v12_kernel', r'kernelILi\dELi\dELb1E', 128, 108),
     # attention: 128 MFMAs + 64 exp + 64 adds + 32 cvt + 32 LDS reads + 8 buffer loads to LDS + waits / state rotation (235; the variant that
     # scales q in the loop: 299)
-    ('attn_hd128_m16.hip', 'attn_hd128_m16_kernel', r'kernelILb1E', 128, 305),
+    ('attn_hd128_m16.hip', 'attn_hd128_m16_kernel', r'kernelILb1E|ELi5EEv', 128, 305),
+    # the five-query-block instantiation (pre-scaled entry only): 160 MFMAs + 80 exp + 80 adds + 40 cvt + 32 LDS reads + 8 buffer loads to
+    # LDS + the same waits / state rotation (275)
+    ('attn_hd128_m16.hip', 'attn_hd128_m16_kernel', r'kernelILb1E|ELi4EEv', 160, 285),
 ]
 FORBIDDEN = ('scratch_', 'v_cndmask', 'v_readfirstlane')
 MAX_ACC_MOVES = 8      # v_accvgpr_read / _write per iteration (register-file shuffles of a kernel at the 512-register limit)

@@ -11,7 +11,8 @@ Rows: the shipped attention kernel (filler placement 1, items by ticket) and its
 round-2 kernel w64); the SAME shipped binary on operands that do not toggle (all zero / one constant): the instruction stream is identical, only the
 switching activity differs — what the power limit itself costs; GEMM variants 12 (shipped) / 11 / 8 on the o-projection and ffn.0 shapes, random and zero A.
 
-    python tools/energy_table.py [--secs 6] [--heads 8] [--only attn|gemm]          (A/B library: measurement only)
+    python tools/energy_table.py [--secs 6] [--heads 8] [--only attn|gemm|nq]       (A/B library: measurement only; nq = only the rows that
+                                                                                     compare four and five query blocks per wave, alternating)
 """
 import argparse
 import json
@@ -29,7 +30,7 @@ from wan.backend import lib, ops  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument('--secs', type=float, default=6.0)
 ap.add_argument('--heads', type=int, default=8)
-ap.add_argument('--only', default=None, choices=['attn', 'gemm'])
+ap.add_argument('--only', default=None, choices=['attn', 'gemm', 'nq'])
 ap.add_argument('--L', type=int, default=131040)
 args = ap.parse_args()
 dev = torch.device('cuda:0')
@@ -68,7 +69,7 @@ def loop(label, fn, flops, group=4):
 
 
 with lib.ab_library() as h:
-    if args.only in (None, 'attn'):
+    if args.only in (None, 'attn', 'nq'):
         heads = args.heads
         g = torch.Generator(device=dev).manual_seed(1234)
         q = torch.randn(L, heads * 128, device=dev, generator=g).bfloat16()
@@ -82,7 +83,13 @@ with lib.ab_library() as h:
         def attn():
             ops.attention_hd128(q, kp, vp, o, L, heads, 1.0, prescaled=True)
         ops.pack_kv(k, v, heads, kp, vp)
-        loop('attention m16, shipped (placement 1's gaps, MFMAs in quads, tickets), random operands', attn, fl)
+        for _ in range(2):          # 256- against 320-query items on the same operands, alternating (debug bits 8 / 7 force the item size)
+            for name, dbg in (('FOUR query blocks per wave forced (256-query items)', 256), ('FIVE query blocks per wave forced (320-query items)', 128)):
+                h.mg_attn_w64_debug(dbg)
+                loop(f'attention m16, {name}, random operands', attn, fl)
+        h.mg_attn_w64_debug(0)
+    if args.only in (None, 'attn'):
+        loop("attention m16, shipped (placement 1's gaps, MFMAs in quads, tickets), random operands", attn, fl)
         for name, dbg in (('placement 0 (round-4 order)', 12), ('placement 2', 4), ('placement 3', 6), ('placement 4', 8), ('placement 5', 10),
                           ('shipped placement, STATIC per-XCD partition', 16)):
             h.mg_attn_w64_debug(dbg)
