@@ -540,9 +540,9 @@ __global__ __launch_bounds__(NT) void head_gemm_f32_kernel(const float* __restri
 
 extern "C" int mg_head_gemm_f32(const float* x, int64_t ldx, const float* Wm, const float* bias, float* out,
                                 int64_t M, int N, int K, void* stream) {
-    if (!x || !Wm || !out) return MG_ERR_ARG;
     if (N <= 0 || N > 64 || K <= 0 || M < 0) return MG_ERR_SHAPE;
-    if (M == 0) return MG_OK;
+    if (M == 0) return MG_OK;          // (before the pointers: an empty x or out has none)
+    if (!x || !Wm || !out) return MG_ERR_ARG;
     hipLaunchKernelGGL(head_gemm_f32_kernel, dim3((unsigned)((M + 63) / 64)), dim3(NT), 0,
                        (hipStream_t)stream, x, ldx, Wm, bias, out, M, N, K);
     return mg_check_launch();

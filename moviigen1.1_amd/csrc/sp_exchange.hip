@@ -46,7 +46,7 @@ static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 extern "C" int mg_sp_pack_qkv_bf16(const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ldk, const uint16_t* v,
                                    int64_t ldv, int64_t Lloc, int P, int cols_per_dest, int col0, int w, uint16_t* send,
                                    void* stream) {
-    if (!q || !k || !v || !send) return MG_ERR_ARG;
+    if (Lloc != 0 && (!q || !k || !v || !send)) return MG_ERR_ARG;          // (no rows: the buffers are empty and have no address)
     if (Lloc < 0 || P <= 0 || w <= 0 || (w & 7) || (col0 & 7) || (cols_per_dest & 7) || col0 + w > cols_per_dest ||
         (ldq & 7) || (ldk & 7) || (ldv & 7) || !aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(send))
         return MG_ERR_SHAPE;
@@ -62,7 +62,7 @@ extern "C" int mg_sp_pack_qkv_bf16(const uint16_t* q, int64_t ldq, const uint16_
 
 extern "C" int mg_sp_unpack_o_bf16(const uint16_t* recv, int64_t Lloc, int P, int cols_per_src, int col0, int w, uint16_t* o,
                                    int64_t ldo, void* stream) {
-    if (!recv || !o) return MG_ERR_ARG;
+    if (Lloc != 0 && (!recv || !o)) return MG_ERR_ARG;
     if (Lloc < 0 || P <= 0 || w <= 0 || (w & 7) || (col0 & 7) || (cols_per_src & 7) || col0 + w > cols_per_src || (ldo & 7) ||
         !aligned16(recv) || !aligned16(o))
         return MG_ERR_SHAPE;
@@ -71,7 +71,7 @@ extern "C" int mg_sp_unpack_o_bf16(const uint16_t* recv, int64_t Lloc, int P, in
 
 extern "C" int mg_sp_copy_blocks_bf16(const uint16_t* src, int64_t s_blk, int64_t s_row, uint16_t* dst, int64_t d_blk,
                                       int64_t d_row, int blocks, int64_t rows, int width, void* stream) {
-    if (!src || !dst) return MG_ERR_ARG;
+    if (blocks != 0 && rows != 0 && (!src || !dst)) return MG_ERR_ARG;
     if (blocks < 0 || rows < 0 || width <= 0 || (width & 7) || (s_blk & 7) || (s_row & 7) || (d_blk & 7) || (d_row & 7) ||
         !aligned16(src) || !aligned16(dst))
         return MG_ERR_SHAPE;

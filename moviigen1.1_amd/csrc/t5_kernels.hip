@@ -21,9 +21,9 @@ __global__ void t5_embed_kernel(const uint16_t* __restrict__ table, const int64_
 
 extern "C" int mg_embed_rows_bf16(const uint16_t* table, int64_t vocab, int dim, const int64_t* ids, int n,
                                   uint16_t* out, void* stream) {
-    if (!table || !ids || !out) return MG_ERR_ARG;
     if (n < 0 || dim <= 0 || (dim & 7) || vocab <= 0) return MG_ERR_SHAPE;
-    if (n == 0) return MG_OK;
+    if (n == 0) return MG_OK;          // (before the pointers: empty ids and out have none)
+    if (!table || !ids || !out) return MG_ERR_ARG;
     hipLaunchKernelGGL(t5_embed_kernel, dim3(n), dim3(128), 0, (hipStream_t)stream, table, ids, out, n, dim, vocab);
     return mg_check_launch();
 }

@@ -34,6 +34,24 @@ def _chk(t, dtype, name):
         raise lib.MoviigenHipError(f'{name}: innermost dimension must be contiguous')
 
 
+def _chk_flat(t, dtype, name, optional=False):
+    """a tensor its kernel reads or writes flat, or with a row stride the C ABI does not carry: _chk, and dense row-major"""
+    if t is None and not optional:
+        raise lib.MoviigenHipError(f'{name}: expected a tensor, got None')
+    _chk(t, dtype, name)
+    if t is not None and not t.is_contiguous():
+        raise lib.MoviigenHipError(f'{name}: must be contiguous, got shape {tuple(t.shape)} with strides {tuple(t.stride())}')
+
+
+def _chk_rows(t, dtype, name):
+    """a [rows, cols] tensor whose row stride goes to the kernel: _chk, two dimensions, rows that do not overlap"""
+    if t is None:
+        raise lib.MoviigenHipError(f'{name}: expected a tensor, got None')
+    _chk(t, dtype, name)
+    if t.dim() != 2 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise lib.MoviigenHipError(f'{name}: expected [rows, cols] with a row stride >= cols, got shape {tuple(t.shape)} with strides {tuple(t.stride())}')
+
+
 def ln_modulate(x, scale, shift, add_one, eps, out, round_norm_bf16=False):
     """x [rows, dim] fp32 -> out [rows, dim] (bf16 or fp32)."""
     _chk(x, torch.float32, 'x'); _chk(scale, torch.float32, 'scale'); _chk(shift, torch.float32, 'shift')
@@ -256,52 +274,91 @@ def attention_generic(q, k, v, out, lk, heads, head_dim, scale):
 
 
 def sinusoid_embed(t, dim, out):
+    """t [n] int64 / fp32 / fp64 positions -> out [n, dim] fp32 = cos(t w_j) | sin(t w_j), w_j = 10000^(-j / (dim/2)), evaluated in fp64."""
     code = {torch.int64: 0, torch.float32: 1, torch.float64: 2}.get(t.dtype)
-    if code is None or not t.is_cuda:
-        raise lib.MoviigenHipError('timestep must be a CUDA int64/float32/float64 tensor')
-    lib.call('mg_sinusoid_embed', _p(t), code, t.numel(), int(dim), _p(out), _st())
+    if code is None or not t.is_cuda or not t.is_contiguous():
+        raise lib.MoviigenHipError('timestep must be a contiguous CUDA int64/float32/float64 tensor')
+    _chk_flat(out, torch.float32, 'out')
+    dim = int(dim)
+    if dim <= 0 or dim % 2 or out.numel() != t.numel() * dim:
+        raise lib.MoviigenHipError(f'sinusoid_embed: dim {dim} must be even and out {tuple(out.shape)} hold {t.numel()} rows of it')
+    lib.call('mg_sinusoid_embed', _p(t), code, t.numel(), dim, _p(out), _st())
     return out
 
 
 def gemv(w, bias, x, y, silu_in=False):
-    _chk(w, torch.float32, 'w'); _chk(x, torch.float32, 'x'); _chk(y, torch.float32, 'y')
+    """y [N] = w [N, K] @ (silu(x) if silu_in else x) [K] + bias [N] (None = 0): dense fp32 tensors, K a multiple of 4."""
+    _chk_flat(w, torch.float32, 'w'); _chk_flat(bias, torch.float32, 'bias', optional=True)
+    _chk_flat(x, torch.float32, 'x'); _chk_flat(y, torch.float32, 'y')
+    if w.dim() != 2 or w.shape[1] % 4 or x.numel() != w.shape[1] or y.numel() != w.shape[0] or (bias is not None and bias.numel() != w.shape[0]):
+        raise lib.MoviigenHipError(f'gemv shape mismatch w{tuple(w.shape)} (K a multiple of 4) x{tuple(x.shape)} y{tuple(y.shape)}'
+                                   + ('' if bias is None else f' bias{tuple(bias.shape)}'))
     lib.call('mg_gemv_f32', _p(w), _p(bias), _p(x), _p(y), w.shape[0], w.shape[1], int(silu_in), _st())
     return y
 
 
 def add_rows(a, b, out, period):
+    """out [rows, dim] = a [rows, dim] + b [>= period, dim] with row r of a meeting row r % period of b: dense fp32 tensors."""
+    _chk_flat(a, torch.float32, 'a'); _chk_flat(b, torch.float32, 'b'); _chk_flat(out, torch.float32, 'out')
+    period = int(period)
+    if a.dim() != 2 or b.dim() != 2 or period < 1 or b.shape[0] < period or b.shape[1] != a.shape[1] or tuple(out.shape) != tuple(a.shape):
+        raise lib.MoviigenHipError(f'add_rows shape mismatch a{tuple(a.shape)} b{tuple(b.shape)} out{tuple(out.shape)} period {period}')
     rows, dim = a.shape
-    lib.call('mg_add_rows_f32', _p(a), _p(b), _p(out), rows, dim, int(period), _st())
+    lib.call('mg_add_rows_f32', _p(a), _p(b), _p(out), rows, dim, period, _st())
     return out
 
 
 def head_gemm(x, w, bias, out):
-    _chk(x, torch.float32, 'x'); _chk(w, torch.float32, 'w'); _chk(out, torch.float32, 'out')
+    """out [M, N <= 64] = x [M, K] @ w [N, K]^T + bias [N] (None = 0) in fp32: x may be a column slice (row stride free), w and out are dense."""
+    _chk_rows(x, torch.float32, 'x'); _chk_flat(w, torch.float32, 'w'); _chk_flat(bias, torch.float32, 'bias', optional=True)
+    _chk_flat(out, torch.float32, 'out')
+    if w.dim() != 2 or w.shape[0] > 64 or w.shape[1] != x.shape[1] or tuple(out.shape) != (x.shape[0], w.shape[0]) \
+            or (bias is not None and bias.numel() != w.shape[0]):
+        raise lib.MoviigenHipError(f'head_gemm shape mismatch x{tuple(x.shape)} w{tuple(w.shape)} (N <= 64) out{tuple(out.shape)}'
+                                   + ('' if bias is None else f' bias{tuple(bias.shape)}'))
     lib.call('mg_head_gemm_f32', _p(x), x.stride(0), _p(w), _p(bias), _p(out), x.shape[0], w.shape[0], w.shape[1],
              _st())
     return out
 
 
 def patchify(lat, ph, pw, out):
-    _chk(lat, torch.float32, 'lat'); _chk(out, torch.bfloat16, 'out')
+    """lat [C, F, H, W] fp32 dense -> out [>= F (H/ph) (W/pw), >= C ph pw] bf16 (row stride free): row = patch in (f, h, w) order,
+    column = (c, i, j); columns behind C ph pw are not written."""
+    _chk_flat(lat, torch.float32, 'lat'); _chk_rows(out, torch.bfloat16, 'out')
+    ph, pw = int(ph), int(pw)
+    if lat.dim() != 4 or ph < 1 or pw < 1 or lat.shape[2] % ph or lat.shape[3] % pw:
+        raise lib.MoviigenHipError(f'patchify: lat {tuple(lat.shape)} is not [C, F, H, W] with H, W multiples of the patch {(ph, pw)}')
     C, F, H, W = lat.shape
-    lib.call('mg_patchify_bf16', _p(lat), C, F, H, W, int(ph), int(pw), _p(out), out.stride(0), _st())
+    if out.shape[0] < F * (H // ph) * (W // pw) or out.shape[1] < C * ph * pw:
+        raise lib.MoviigenHipError(f'patchify: out {tuple(out.shape)} is smaller than [{F * (H // ph) * (W // pw)}, {C * ph * pw}]')
+    lib.call('mg_patchify_bf16', _p(lat), C, F, H, W, ph, pw, _p(out), out.stride(0), _st())
     return out
 
 
 def unpatchify(tok, C, F, Hg, Wg, ph, pw, lat):
-    _chk(tok, torch.float32, 'tok'); _chk(lat, torch.float32, 'lat')
-    lib.call('mg_unpatchify_f32', _p(tok), tok.stride(0), C, F, Hg, Wg, int(ph), int(pw), _p(lat), _st())
+    """tok [>= F Hg Wg, >= ph pw C] fp32 (row stride free), column = (i, j, c) -> lat [C, F, Hg ph, Wg pw] fp32 dense."""
+    _chk_rows(tok, torch.float32, 'tok'); _chk_flat(lat, torch.float32, 'lat')
+    C, F, Hg, Wg, ph, pw = (int(v) for v in (C, F, Hg, Wg, ph, pw))
+    if min(C, F, Hg, Wg, ph, pw) < 1 or tok.shape[0] < F * Hg * Wg or tok.shape[1] < ph * pw * C or lat.numel() != C * F * Hg * ph * Wg * pw:
+        raise lib.MoviigenHipError(f'unpatchify: tok {tuple(tok.shape)}, lat {tuple(lat.shape)} do not fit (C, F, Hg, Wg, ph, pw) = '
+                                   f'{(C, F, Hg, Wg, ph, pw)}')
+    lib.call('mg_unpatchify_f32', _p(tok), tok.stride(0), C, F, Hg, Wg, ph, pw, _p(lat), _st())
     return lat
 
 
 def lincomb(out, terms):
-    """out = sum(c_i * x_i) for up to 4 (tensor, coef) terms."""
-    terms = list(terms) + [(None, 0.0)] * (4 - len(terms))
+    """out = sum(c_i * x_i) for 1 to 4 (tensor, coef) terms: dense fp32 tensors of out's size."""
+    terms = list(terms)
+    _chk_flat(out, torch.float32, 'out')
+    if not 1 <= len(terms) <= 4:
+        raise lib.MoviigenHipError(f'lincomb takes 1 to 4 terms, got {len(terms)}')
     args = []
-    for x, c in terms:
-        _chk(x, torch.float32, 'x')
+    for i, (x, c) in enumerate(terms):
+        _chk_flat(x, torch.float32, f'x{i}')
+        if x.numel() != out.numel():
+            raise lib.MoviigenHipError(f'lincomb size mismatch out{tuple(out.shape)} x{i}{tuple(x.shape)}')
         args += [_p(x), float(c)]
+    args += [None, 0.0] * (4 - len(terms))
     lib.call('mg_lincomb4_f32', _p(out), out.numel(), *args, _st())
     return out
 
@@ -323,14 +380,21 @@ def lora_merge(w, up, down):
 
 
 def cfg_combine(out, uncond, cond, g):
-    _chk(uncond, torch.float32, 'uncond'); _chk(cond, torch.float32, 'cond')
+    """out = uncond + g * (cond - uncond): dense fp32 tensors of one size."""
+    _chk_flat(out, torch.float32, 'out'); _chk_flat(uncond, torch.float32, 'uncond'); _chk_flat(cond, torch.float32, 'cond')
+    if uncond.numel() != out.numel() or cond.numel() != out.numel():
+        raise lib.MoviigenHipError(f'cfg_combine size mismatch out{tuple(out.shape)} uncond{tuple(uncond.shape)} cond{tuple(cond.shape)}')
     lib.call('mg_cfg_combine_f32', _p(out), _p(uncond), _p(cond), float(g), out.numel(), _st())
     return out
 
 
 # ---- umT5 encoder glue ---------------------------------------------------------------------------
 def embed_rows(table, ids, out):
-    _chk(table, torch.bfloat16, 'table'); _chk(ids, torch.int64, 'ids'); _chk(out, torch.bfloat16, 'out')
+    """out [n, dim] = table [vocab, dim][ids [n]] (ids clamped to the table): dense bf16 / int64 tensors, dim a multiple of 8."""
+    _chk_flat(table, torch.bfloat16, 'table'); _chk_flat(ids, torch.int64, 'ids'); _chk_flat(out, torch.bfloat16, 'out')
+    if table.dim() != 2 or table.shape[0] < 1 or table.shape[1] % 8 or tuple(out.shape) != (ids.numel(), table.shape[1]):
+        raise lib.MoviigenHipError(f'embed_rows shape mismatch table{tuple(table.shape)} (dim a multiple of 8) ids{tuple(ids.shape)} '
+                                   f'out{tuple(out.shape)}')
     lib.call('mg_embed_rows_bf16', _p(table), table.shape[0], table.shape[1], _p(ids), ids.numel(), _p(out), _st())
     return out
 
@@ -630,33 +694,58 @@ def gate_residual(x, y, gate=None):
     return x
 
 
+def _sp_chk_cols(what, P, cols, col0, w):
+    if P < 1 or w < 1 or w % 8 or col0 < 0 or col0 % 8 or cols % 8 or col0 + w > cols:
+        raise lib.MoviigenHipError(f'{what}: columns [{col0}, {col0} + {w}) of {P} blocks of {cols} — all multiples of 8 (16-byte vectors), '
+                                   'inside the block')
+
+
 def sp_pack_qkv(q, k, v, P, cols_per_dest, col0, w, send):
     """q, k, v [Lloc, >= P*cols_per_dest] bf16 (column slices ok) -> send [P, Lloc, 3w] (see moviigen_hip.h)."""
-    for n, t in (('q', q), ('k', k), ('v', v), ('send', send)):
-        _chk(t, torch.bfloat16, n)
+    for n, t in (('q', q), ('k', k), ('v', v)):
+        _chk_rows(t, torch.bfloat16, n)
+    _chk_flat(send, torch.bfloat16, 'send')
+    P, cols_per_dest, col0, w = int(P), int(cols_per_dest), int(col0), int(w)
+    _sp_chk_cols('sp_pack_qkv', P, cols_per_dest, col0, w)
     Lloc = q.shape[0]
-    if send.numel() < P * Lloc * 3 * w or not send.is_contiguous():
-        raise lib.MoviigenHipError('send buffer too small / not contiguous')
-    lib.call('mg_sp_pack_qkv_bf16', _p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), Lloc, int(P),
-             int(cols_per_dest), int(col0), int(w), _p(send), _st())
+    if k.shape[0] != Lloc or v.shape[0] != Lloc or min(q.shape[1], k.shape[1], v.shape[1]) < P * cols_per_dest:
+        raise lib.MoviigenHipError(f'sp_pack_qkv: q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)} must have one row count and >= '
+                                   f'{P} x {cols_per_dest} columns')
+    if send.numel() < P * Lloc * 3 * w:
+        raise lib.MoviigenHipError(f'sp_pack_qkv: send {tuple(send.shape)} is smaller than [{P}, {Lloc}, {3 * w}]')
+    lib.call('mg_sp_pack_qkv_bf16', _p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), Lloc, P, cols_per_dest, col0, w,
+             _p(send), _st())
     return send
 
 
 def sp_unpack_o(recv, P, cols_per_src, col0, w, o):
     """recv [P, Lloc, w] bf16 -> o[:, p*cols_per_src + col0 : +w] for every source rank p."""
-    _chk(recv, torch.bfloat16, 'recv'); _chk(o, torch.bfloat16, 'o')
+    _chk_flat(recv, torch.bfloat16, 'recv'); _chk_rows(o, torch.bfloat16, 'o')
+    P, cols_per_src, col0, w = int(P), int(cols_per_src), int(col0), int(w)
+    _sp_chk_cols('sp_unpack_o', P, cols_per_src, col0, w)
     Lloc = o.shape[0]
-    if recv.numel() < P * Lloc * w or not recv.is_contiguous():
-        raise lib.MoviigenHipError('recv buffer too small / not contiguous')
-    lib.call('mg_sp_unpack_o_bf16', _p(recv), Lloc, int(P), int(cols_per_src), int(col0), int(w), _p(o), o.stride(0), _st())
+    if o.shape[1] < P * cols_per_src:
+        raise lib.MoviigenHipError(f'sp_unpack_o: o {tuple(o.shape)} is narrower than {P} x {cols_per_src} columns')
+    if recv.numel() < P * Lloc * w:
+        raise lib.MoviigenHipError(f'sp_unpack_o: recv {tuple(recv.shape)} is smaller than [{P}, {Lloc}, {w}]')
+    lib.call('mg_sp_unpack_o_bf16', _p(recv), Lloc, P, cols_per_src, col0, w, _p(o), o.stride(0), _st())
     return o
 
 
 def sp_copy_blocks(src, s_blk, s_row, dst, d_blk, d_row, blocks, rows, width):
-    """dst[b][r][:width] = src[b][r][:width] with element strides (*_blk, *_row): the reshapes around an all-to-all."""
+    """dst[b][r][:width] = src[b][r][:width] with element strides (*_blk, *_row) from each tensor's first element: the reshapes around an
+    all-to-all.  Every element addressed has to lie inside the tensor's storage."""
     _chk(src, torch.bfloat16, 'src'); _chk(dst, torch.bfloat16, 'dst')
-    lib.call('mg_sp_copy_blocks_bf16', _p(src), int(s_blk), int(s_row), _p(dst), int(d_blk), int(d_row), int(blocks),
-             int(rows), int(width), _st())
+    s_blk, s_row, d_blk, d_row, blocks, rows, width = (int(v) for v in (s_blk, s_row, d_blk, d_row, blocks, rows, width))
+    if src is None or dst is None or blocks < 0 or rows < 0 or width < 1 or width % 8 or min(s_blk, s_row, d_blk, d_row) < 0:
+        raise lib.MoviigenHipError(f'sp_copy_blocks: {blocks} blocks of {rows} rows of {width} (a multiple of 8) with strides '
+                                   f'{(s_blk, s_row)} -> {(d_blk, d_row)}')
+    for n, t, blk, row in (('src', src, s_blk, s_row), ('dst', dst, d_blk, d_row)):
+        last = (blocks - 1) * blk + (rows - 1) * row + width - 1
+        if blocks and rows and t.storage_offset() + last >= t.untyped_storage().nbytes() // t.element_size():
+            raise lib.MoviigenHipError(f'sp_copy_blocks: element {last} of {n} {tuple(t.shape)} (block {blocks - 1}, row {rows - 1}, column '
+                                       f'{width - 1}) lies outside its storage')
+    lib.call('mg_sp_copy_blocks_bf16', _p(src), s_blk, s_row, _p(dst), d_blk, d_row, blocks, rows, width, _st())
     return dst
 
 

@@ -342,7 +342,7 @@ class WanT2V:
         if noise is None:
             noise = torch.randn(*target_shape, dtype=torch.float32, device=self.device, generator=seed_g)
         else:
-            noise = noise.to(self.device, torch.float32)
+            noise = noise.to(self.device, torch.float32).contiguous()       # (the latent kernels work on dense memory; a permuted view is copied here)
             assert tuple(noise.shape) == tuple(target_shape)
 
         with torch.no_grad():

@@ -19,7 +19,8 @@ __all__ = ['FlowUniPCMultistepScheduler']
 
 def _hip_lincomb(like, terms):
     from ..backend import ops
-    out = torch.empty_like(like)
+    # the kernel works on flat memory: the terms are made dense here, and so is the result (empty_like alone keeps the strides of a permuted `like`)
+    out = torch.empty_like(like, memory_format=torch.contiguous_format)
     return ops.lincomb(out, [(t.contiguous(), c) for t, c in terms])
 
 

@@ -404,24 +404,7 @@ def attn_variant(request):
         yield request.param
 
 
-def test_small_fp32_kernels(dev):
-    from oracle import dit
-    from wan.backend import ops
-    # sinusoid (model.py:15-25)
-    t = torch.tensor([999, 500, 3])
-    out = torch.empty(3, 256, dtype=torch.float32, device=dev)
-    ops.sinusoid_embed(t.to(dev), 256, out)
-    assert scale_err(out, dit.sinusoid(256, t).float()) < 1e-6
-    # unpatchify vs golden-checked oracle
-    tok = W.randn((24, 64), 13)
-    lat = torch.empty(16, 2, 6, 8, dtype=torch.float32, device=dev)
-    ops.unpatchify(tok.to(dev), 16, 2, 3, 4, 2, 2, lat)
-    assert torch.equal(lat.cpu(), dit.unpatchify(tok, (2, 3, 4), (1, 2, 2), 16))
-    # cfg combine, exact op order of text2video.py:245-246
-    u, c = W.randn((1000,), 20), W.randn((1000,), 21)
-    o = torch.empty(1000, dtype=torch.float32, device=dev)
-    ops.cfg_combine(o, u.to(dev), c.to(dev), 5.0)
-    assert scale_err(o, u + 5.0 * (c - u)) < 1e-6
+# (sinusoid_embed, unpatchify, cfg_combine and the other small fp32 / layout kernels: tests/test_small_kernels.py)
 
 
 # ------------------------------------------------------------------------------------------------
