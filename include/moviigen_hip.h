@@ -367,7 +367,7 @@ int mg_t5_attn_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int
  * (kh/2, kw/2).  `up2`: the input is read through a nearest-exact 2x upsample (Ho=2H, Wo=2W;
  * Resample upsample2d/3d, vae.py:66-83,138-141).  residual (same shape as out, may be NULL) is
  * added (ResidualBlock `x + h`, vae.py:220).  kt <= 3, kh and kw in {1, 3} (what WanVAE uses); larger extents return
- * MG_ERR_SHAPE. */
+ * MG_ERR_SHAPE.  So does Cout > 4 that is not a multiple of 4, in every convolution below (rows of out / residual move as float4). */
 int mg_vae_conv_f32(const float* x, const float* cache, int tc, int T, int H, int W, int Cin,
                     const float* w, const float* bias, int Cout, int kt, int kh, int kw, int up2,
                     const float* residual, float* out, int mode, void* stream);
@@ -411,7 +411,8 @@ int mg_vae_upconv_phases_cols_f32(const float* x, int T, int H, int W, int Cin, 
 #define MG_VAE_TILE_256 (2 << 8)
 
 /* RMS_norm over channels (F.normalize(x, dim=C) * sqrt(C) * gamma, vae.py:39-54), optional SiLU
- * (vae.py:193-197, 466-468).  x,out [rows][C] channels-last. */
+ * (vae.py:193-197, 466-468).  x,out [rows][C] channels-last; C % 4 == 0, C <= 512, and x, gamma, out 16-byte aligned
+ * (they are read and written as float4): anything else returns MG_ERR_SHAPE. */
 int mg_vae_rmsnorm_silu_f32(const float* x, const float* gamma, float* out, int64_t rows, int C,
                             int do_silu, void* stream);
 
@@ -419,7 +420,8 @@ int mg_vae_rmsnorm_silu_f32(const float* x, const float* gamma, float* out, int6
  * AttentionBlock, vae.py:247-256 (scaled_dot_product_attention, scale 1/sqrt(C)).
  * qkv [frames][L][3C] (q|k|v), out [frames][L][C]; workspace: caller-owned, mg_vae_attn_workspace_floats(L, C)
  * floats = (min(L, 2048) + C) * roundup(L, 4) — one block of 2048 query rows of the score matrix, which stays
- * inside the Infinity Cache between the three passes, plus V^T — 16-byte aligned (the library never allocates). */
+ * inside the Infinity Cache between the three passes, plus V^T — 16-byte aligned (the library never allocates); qkv and
+ * out 16-byte aligned too (MG_ERR_SHAPE otherwise: out is written as float4). */
 int64_t mg_vae_attn_workspace_floats(int64_t L, int C);
 int mg_vae_attn_f32(const float* qkv, float* out, int frames, int64_t L, int C, float* workspace,
                     void* stream);

@@ -77,7 +77,8 @@ MG_DEV void cv_epilogue(const ConvArgs& a, const f32x16_t (&acc)[NB], int64_t m_
             if (fullw || n + 3 < a.Cout) {
                 if (a.bias) b4[c] = *(const float4*)(a.bias + n);
                 if (a.residual) r4[c] = *(const float4*)(a.residual + m * a.ldo + n);
-            } else {
+            } else {      // a quad that crosses Cout: rows of Cout <= 4 (ldo = Cout, phase form and encoder gathers) and the score GEMM at L % 4 != 0 — none
+                          // of them has a residual today (launch_conv refuses the other ragged rows), so the residual line below is kept for symmetry only
                 float* bb = (float*)&b4[c];
                 float* rp = (float*)&r4[c];
 #pragma unroll
@@ -265,7 +266,9 @@ __global__ __launch_bounds__(CV_THREADS) void vae_conv_kernel(const ConvArgs a) 
         const int c = c_ok ? c_raw : 0;
 #pragma unroll
         for (int i = 0; i < NR; ++i) {         // (loaded as an ext-vector: a float4 struct copy from a selected pointer kept ra / rw in memory)
-            const f32x4_t t = *(const f32x4_t*)(pa[i] + c);                   // k >= Cin: finite data x zero weights
+            // k >= Cin re-reads channels 0-3 of the same voxel against zero weights: exact for finite data.  An Inf there becomes NaN (Inf x 0) in
+            // the outputs that read this voxel, where the reference gives +-Inf (or a number, if its weights for those channels are zero)
+            const f32x4_t t = *(const f32x4_t*)(pa[i] + c);
             ra[i] = make_float4(t[0], t[1], t[2], t[3]);
         }
 #pragma unroll
@@ -461,6 +464,10 @@ __global__ __launch_bounds__(256) void vae_ksplit_reduce_kernel(const float* __r
 static int launch_conv(const ConvArgs& a, hipStream_t st, int mode, int gather = CV_G_PLAIN) {
     if ((int64_t)(a.T > a.tc ? a.T : a.tc) * a.H * a.W > 0x7fffffffLL) return MG_ERR_SHAPE;   // 32-bit voxel index in the gather
     if (a.kt * a.kh * a.kw > 1 && a.Cin > 1024) return MG_ERR_SHAPE;                           // padding taps index the zero page by channel
+    // cv_epilogue moves the whole quads of a row as float4 at out / residual + m * ldo + n: with more than one quad per row (Cout > 4) the row
+    // stride has to keep them 16-byte aligned.  For the convolutions ldo = Cout: Cout > 4 is a multiple of 4 or refused (rows of Cout <= 4 go
+    // element by element; the attention GEMMs pad their row stride)
+    if (a.Cout > 4 && (a.ldo & 3)) return MG_ERR_SHAPE;
     int nb;
     if (a.Cout <= 4 && !a.phases && a.ksplit <= 1 && gather == CV_G_PLAIN) nb = 0;        // the decoder head (96 -> 3): v_mfma_f32_4x4x1, exact in either mode
     else if (a.Cout <= 32) nb = 1;
@@ -682,6 +689,7 @@ extern "C" int mg_vae_rmsnorm_silu_f32(const float* x, const float* gamma, float
                                        int do_silu, void* stream) {
     if (!x || !gamma || !out) return MG_ERR_ARG;
     if (C <= 0 || (C & 3) || C > 512 || rows < 0) return MG_ERR_SHAPE;
+    if (((uintptr_t)x & 15) || ((uintptr_t)gamma & 15) || ((uintptr_t)out & 15)) return MG_ERR_SHAPE;      // all three go as float4
     if (rows == 0) return MG_OK;
     int64_t g = (rows + 3) / 4;
     if (g > 65536 * 8) g = 65536 * 8;
@@ -765,7 +773,7 @@ static int vae_attn_impl(const float* q, int64_t ldq, int64_t q_fs, const float*
                          int frames, int64_t Lq, int64_t L, int C, float* workspace, void* stream) {
     if (!q || !k || !v || !out || !workspace) return MG_ERR_ARG;
     if (frames <= 0 || L <= 0 || Lq <= 0 || Lq > L || C <= 0 || (C & 3) || L > 0x7ffffff0LL || (ldq & 3) || (ldkv & 3)) return MG_ERR_SHAPE;
-    if (((uintptr_t)workspace & 15) || ((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15)) return MG_ERR_SHAPE;
+    if (((uintptr_t)workspace & 15) || ((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15)) return MG_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     const int64_t Lp = (L + 3) & ~(int64_t)3;  // row stride of S / V^T, 16-byte aligned rows
     const int64_t QB = L < VAE_ATTN_QB ? L : VAE_ATTN_QB;

@@ -426,13 +426,56 @@ def t5_attention(q, k, v, rel_emb, rel_bucket, out, lk, heads, head_dim):
 VAE_EXACT, VAE_BF16X3 = 0, 1     # MG_VAE_EXACT / MG_VAE_BF16X3 (include/moviigen_hip.h): the arithmetic of one convolution call
 
 
+def _vae_err(what, msg):
+    raise lib.MoviigenHipError(f'{what}: {msg}')
+
+
+def _vae_conv_geometry(what, x, w, bias, cache, kernel):
+    """the operands every VAE convolution shares: x [T,H,W,Cin] dense; w dense, [Cout,kt,kh,kw,Cin] for kernel = (kt, kh, kw) or the folded
+    [4,Cout,2,2,Cin] for kernel = 'phases'; bias of Cout floats; cache dense, at most kt - 1 frames of x's geometry.
+    -> (T, H, W, Cin, Cout, tc)"""
+    _chk_flat(x, torch.float32, f'{what}: x')
+    _chk_flat(w, torch.float32, f'{what}: w')
+    _chk_flat(bias, torch.float32, f'{what}: bias', optional=True)
+    _chk_flat(cache, torch.float32, f'{what}: cache', optional=True)
+    if x.dim() != 4 or w.dim() != 5:
+        _vae_err(what, f'x must be [T, H, W, Cin] and w have five dimensions, got {tuple(x.shape)} and {tuple(w.shape)}')
+    T, H, W, Cin = x.shape
+    if kernel == 'phases':
+        Cout, kt = w.shape[1], 1
+        want = (4, Cout, 2, 2, Cin)
+    else:
+        Cout, kt = w.shape[0], kernel[0]
+        want = (Cout, *kernel, Cin)
+    if tuple(w.shape) != want:
+        _vae_err(what, f'w must be {want} for x {tuple(x.shape)}, got {tuple(w.shape)}')
+    if Cout > 4 and Cout % 4:
+        _vae_err(what, f'Cout = {Cout}: more than 4 output channels have to be a multiple of 4 (the rows of out and residual move as float4)')
+    if bias is not None and bias.numel() != Cout:
+        _vae_err(what, f'bias has {bias.numel()} elements, Cout is {Cout}')
+    tc = 0
+    if cache is not None:
+        if cache.dim() != 4 or tuple(cache.shape[1:]) != (H, W, Cin) or cache.shape[0] > kt - 1:
+            _vae_err(what, f'the cache must be at most {kt - 1} frames with the frame geometry of x {tuple(x.shape)}, got {tuple(cache.shape)}')
+        tc = cache.shape[0]
+    return T, H, W, Cin, Cout, tc
+
+
+def _vae_conv_out(what, out, residual, want):
+    """out, and residual when given: dense fp32 of exactly the shape the kernel writes"""
+    _chk_flat(out, torch.float32, f'{what}: out')
+    _chk_flat(residual, torch.float32, f'{what}: residual', optional=True)
+    for n, t in (('out', out), ('residual', residual)):
+        if t is not None and tuple(t.shape) != want:
+            _vae_err(what, f'{n} must be {want}, got {tuple(t.shape)}')
+
+
 def vae_conv(x, w, bias, out, kt, kh, kw, cache=None, up2=False, residual=None, mode=VAE_EXACT):
     """x [T,H,W,Cin]; w [Cout,kt,kh,kw,Cin]; out [T,Ho,Wo,Cout]."""
-    for n, t in (('x', x), ('w', w), ('bias', bias), ('out', out), ('cache', cache), ('residual', residual)):
-        _chk(t, torch.float32, n)
-    T, H, W, Cin = x.shape
-    tc = 0 if cache is None else cache.shape[0]
-    lib.call('mg_vae_conv_f32', _p(x), _p(cache), tc, T, H, W, Cin, _p(w), _p(bias), w.shape[0], kt, kh, kw,
+    kt, kh, kw = int(kt), int(kh), int(kw)
+    T, H, W, Cin, Cout, tc = _vae_conv_geometry('vae_conv', x, w, bias, cache, (kt, kh, kw))
+    _vae_conv_out('vae_conv', out, residual, (T, 2 * H, 2 * W, Cout) if up2 else (T, H, W, Cout))
+    lib.call('mg_vae_conv_f32', _p(x), _p(cache), tc, T, H, W, Cin, _p(w), _p(bias), Cout, kt, kh, kw,
              int(up2), _p(residual), _p(out), int(mode), _st())
     return out
 
@@ -440,23 +483,23 @@ def vae_conv(x, w, bias, out, kt, kh, kw, cache=None, up2=False, residual=None, 
 def vae_conv_cols(x, w, bias, out, kt, kh, kw, col0, cache=None, residual=None, mode=VAE_EXACT):
     """the W-band form: x [T,H,W,Cin] and cache carry the neighbours' halo columns; out (and residual) [T,H,cols,Cout] compact =
     the output columns [col0, col0 + cols) of vae_conv on the whole image."""
-    for n, t in (('x', x), ('w', w), ('bias', bias), ('out', out), ('cache', cache), ('residual', residual)):
-        _chk(t, torch.float32, n)
-    T, H, W, Cin = x.shape
-    cols = out.shape[2]
-    if out.shape[0] != T or out.shape[1] != H or not out.is_contiguous() or not x.is_contiguous():
-        raise lib.MoviigenHipError(f'vae_conv_cols: out {tuple(out.shape)} does not match x {tuple(x.shape)}')
-    if cache is not None and (tuple(cache.shape[1:]) != tuple(x.shape[1:]) or not cache.is_contiguous()):
-        raise lib.MoviigenHipError('vae_conv_cols: the cache must have the haloed geometry of x')
-    tc = 0 if cache is None else cache.shape[0]
-    lib.call('mg_vae_conv_cols_f32', _p(x), _p(cache), tc, T, H, W, Cin, _p(w), _p(bias), w.shape[0], kt, kh, kw,
-             _p(residual), _p(out), int(col0), int(cols), int(mode), _st())
+    kt, kh, kw, col0 = int(kt), int(kh), int(kw), int(col0)
+    T, H, W, Cin, Cout, tc = _vae_conv_geometry('vae_conv_cols', x, w, bias, cache, (kt, kh, kw))
+    _chk_flat(out, torch.float32, 'vae_conv_cols: out')
+    cols = out.shape[2] if out.dim() == 4 else 0
+    if col0 < 0 or cols < 1 or col0 + cols > W:
+        _vae_err('vae_conv_cols', f'columns [{col0}, {col0} + {cols}) of out {tuple(out.shape)} are not inside x {tuple(x.shape)}')
+    _vae_conv_out('vae_conv_cols', out, residual, (T, H, cols, Cout))
+    lib.call('mg_vae_conv_cols_f32', _p(x), _p(cache), tc, T, H, W, Cin, _p(w), _p(bias), Cout, kt, kh, kw,
+             _p(residual), _p(out), col0, int(cols), int(mode), _st())
     return out
 
 
 def vae_upconv_fold_weights(w):
     """w [Cout,1,3,3,Cin] (the conv behind a nearest-2x upsample) -> [4,Cout,2,2,Cin]: one 2x2 kernel per output parity."""
-    _chk(w, torch.float32, 'w')
+    _chk_flat(w, torch.float32, 'vae_upconv_fold_weights: w')
+    if w.dim() != 5:
+        _vae_err('vae_upconv_fold_weights', f'w must be [Cout, 1, 3, 3, Cin], got {tuple(w.shape)}')
     Cout, kt, kh, kw, Cin = w.shape
     if (kt, kh, kw) != (1, 3, 3):
         raise ValueError(f'the phase decomposition is defined for 1x3x3 kernels, got {kt}x{kh}x{kw}')
@@ -467,27 +510,35 @@ def vae_upconv_fold_weights(w):
 
 def vae_upconv_phases(x, wp, bias, out, mode=VAE_EXACT):
     """x [T,H,W,Cin]; wp from vae_upconv_fold_weights; out [T,2H,2W,Cout] = conv3x3(nearest-2x(x))."""
-    for n, t in (('x', x), ('wp', wp), ('bias', bias), ('out', out)):
-        _chk(t, torch.float32, n)
-    T, H, W, Cin = x.shape
-    lib.call('mg_vae_upconv_phases_f32', _p(x), T, H, W, Cin, _p(wp), _p(bias), wp.shape[1], _p(out), int(mode), _st())
+    T, H, W, Cin, Cout, _ = _vae_conv_geometry('vae_upconv_phases', x, wp, bias, None, 'phases')
+    _vae_conv_out('vae_upconv_phases', out, None, (T, 2 * H, 2 * W, Cout))
+    lib.call('mg_vae_upconv_phases_f32', _p(x), T, H, W, Cin, _p(wp), _p(bias), Cout, _p(out), int(mode), _st())
     return out
 
 
 def vae_upconv_phases_cols(x, wp, bias, out, col0, mode=VAE_EXACT):
     """the W-band form of vae_upconv_phases: x [T,H,W,Cin] with halo columns, out [T,2H,2 cols,Cout] compact."""
-    for n, t in (('x', x), ('wp', wp), ('bias', bias), ('out', out)):
-        _chk(t, torch.float32, n)
-    T, H, W, Cin = x.shape
-    if out.shape[0] != T or out.shape[1] != 2 * H or out.shape[2] % 2 or not out.is_contiguous() or not x.is_contiguous():
-        raise lib.MoviigenHipError(f'vae_upconv_phases_cols: out {tuple(out.shape)} does not match x {tuple(x.shape)}')
-    lib.call('mg_vae_upconv_phases_cols_f32', _p(x), T, H, W, Cin, _p(wp), _p(bias), wp.shape[1], _p(out), int(col0), out.shape[2] // 2,
-             int(mode), _st())
+    col0 = int(col0)
+    T, H, W, Cin, Cout, _ = _vae_conv_geometry('vae_upconv_phases_cols', x, wp, bias, None, 'phases')
+    _chk_flat(out, torch.float32, 'vae_upconv_phases_cols: out')
+    cols2 = out.shape[2] if out.dim() == 4 else 1
+    cols = cols2 // 2
+    if cols2 % 2 or col0 < 0 or cols < 1 or col0 + cols > W:
+        _vae_err('vae_upconv_phases_cols', f'out {tuple(out.shape)} is not [T, 2H, 2 cols, Cout] for columns [{col0}, {col0} + cols) inside x {tuple(x.shape)}')
+    _vae_conv_out('vae_upconv_phases_cols', out, None, (T, 2 * H, 2 * cols, Cout))
+    lib.call('mg_vae_upconv_phases_cols_f32', _p(x), T, H, W, Cin, _p(wp), _p(bias), Cout, _p(out), col0, cols, int(mode), _st())
     return out
 
 
 def vae_rmsnorm_silu(x, gamma, out, do_silu=True):
+    """x [..., C] -> out of the same shape: x / max(|x|, 1e-12) * sqrt(C) * gamma over the last dimension, then SiLU when do_silu."""
+    for n, t in (('x', x), ('gamma', gamma), ('out', out)):
+        _chk_flat(t, torch.float32, f'vae_rmsnorm_silu: {n}')
+    if x.dim() < 1 or x.shape[-1] < 1:
+        _vae_err('vae_rmsnorm_silu', f'x must be [..., C], got {tuple(x.shape)}')
     C = x.shape[-1]
+    if gamma.numel() != C or out.shape != x.shape:
+        _vae_err('vae_rmsnorm_silu', f'x {tuple(x.shape)} needs a gamma of {C} elements and an out of its shape, got {tuple(gamma.shape)} and {tuple(out.shape)}')
     lib.call('mg_vae_rmsnorm_silu_f32', _p(x), _p(gamma), _p(out), x.numel() // C, C, int(do_silu), _st())
     return out
 
@@ -497,22 +548,35 @@ def vae_attn_workspace_floats(L, C):
 
 
 def vae_attn(qkv, out, workspace):
+    """qkv [frames, L, 3C] = q | k | v per pixel, out [frames, L, C] = softmax(q k^T / sqrt(C)) v per frame."""
+    for n, t in (('qkv', qkv), ('out', out), ('workspace', workspace)):
+        _chk_flat(t, torch.float32, f'vae_attn: {n}')
+    if qkv.dim() != 3 or qkv.shape[2] % 3 or qkv.shape[2] == 0:
+        _vae_err('vae_attn', f'qkv must be [frames, L, 3C], got {tuple(qkv.shape)}')
     frames, L, C3 = qkv.shape
-    if workspace.numel() < vae_attn_workspace_floats(L, C3 // 3):
+    C = C3 // 3
+    if tuple(out.shape) != (frames, L, C):
+        _vae_err('vae_attn', f'out must be {(frames, L, C)}, got {tuple(out.shape)}')
+    if workspace.numel() < vae_attn_workspace_floats(L, C):
         raise lib.MoviigenHipError('vae_attn workspace too small')
-    lib.call('mg_vae_attn_f32', _p(qkv), _p(out), frames, L, C3 // 3, _p(workspace), _st())
+    lib.call('mg_vae_attn_f32', _p(qkv), _p(out), frames, L, C, _p(workspace), _st())
     return out
 
 
 def vae_attn_rows(q, kv, out, workspace):
     """q [frames, Lq, >= C] (a column slice of the band's q|k|v is fine), kv [frames, Lk, 2C] = k | v of ALL pixels of the frame in image
     order, out [frames, Lq, C]: the band's rows of vae_attn, same bits."""
-    for n, t in (('q', q), ('kv', kv), ('out', out), ('workspace', workspace)):
-        _chk(t, torch.float32, n)
+    _chk(q, torch.float32, 'vae_attn_rows: q')
+    for n, t in (('kv', kv), ('out', out), ('workspace', workspace)):
+        _chk_flat(t, torch.float32, f'vae_attn_rows: {n}')
+    if q is None or q.dim() != 3 or kv.dim() != 3 or kv.shape[2] % 2 or kv.shape[2] == 0:
+        _vae_err('vae_attn_rows', f'q must be [frames, Lq, >= C] and kv [frames, Lk, 2C], got {None if q is None else tuple(q.shape)} and {tuple(kv.shape)}')
     frames, Lq = q.shape[:2]
     Lk, C = kv.shape[1], kv.shape[2] // 2
-    if kv.shape[0] != frames or not kv.is_contiguous() or not out.is_contiguous() or q.stride(0) != Lq * q.stride(1) or out.shape != (frames, Lq, C):
-        raise lib.MoviigenHipError('vae_attn_rows: shapes')
+    if Lq > Lk:
+        _vae_err('vae_attn_rows', f'Lq = {Lq} query rows exceed the Lk = {Lk} keys: the queries are a subset of the frame\'s pixels')
+    if kv.shape[0] != frames or q.shape[2] < C or q.stride(1) < q.shape[2] or q.stride(0) != Lq * q.stride(1) or tuple(out.shape) != (frames, Lq, C):
+        _vae_err('vae_attn_rows', f'shapes: q {tuple(q.shape)} with strides {tuple(q.stride())}, kv {tuple(kv.shape)}, out {tuple(out.shape)}')
     if workspace.numel() < vae_attn_workspace_floats(Lk, C):
         raise lib.MoviigenHipError('vae_attn workspace too small')
     lib.call('mg_vae_attn_rows_f32', _p(q), q.stride(1), _p(kv), ctypes.c_void_p(kv.data_ptr() + 4 * C), 2 * C, _p(out), frames, Lq, Lk, C,
@@ -521,19 +585,42 @@ def vae_attn_rows(q, kv, out, workspace):
 
 
 def vae_latent_in(z, mean, inv_std, out):
+    """z [C,T,H,W] -> out [T,H,W,C] = z / inv_std + mean per channel."""
+    for n, t in (('z', z), ('mean', mean), ('inv_std', inv_std), ('out', out)):
+        _chk_flat(t, torch.float32, f'vae_latent_in: {n}')
+    if z.dim() != 4:
+        _vae_err('vae_latent_in', f'z must be [C, T, H, W], got {tuple(z.shape)}')
     C, T, H, W = z.shape
+    if tuple(out.shape) != (T, H, W, C) or mean.numel() < C or inv_std.numel() < C:
+        _vae_err('vae_latent_in', f'z {tuple(z.shape)} needs out {(T, H, W, C)} and {C} means and scales, got out {tuple(out.shape)}, '
+                                  f'{mean.numel()} and {inv_std.numel()}')
     lib.call('mg_vae_latent_in_f32', _p(z), _p(mean), _p(inv_std), C, T, H, W, _p(out), _st())
     return out
 
 
 def vae_video_out(x, out, t_off):
+    """x [T,H,W,C] -> out[:, t_off:t_off + T] of out [C,T_total,H,W], clamped to [-1, 1] (NaN becomes -1)."""
+    _chk_flat(x, torch.float32, 'vae_video_out: x')
+    _chk_flat(out, torch.float32, 'vae_video_out: out')
+    if x.dim() != 4 or out.dim() != 4:
+        _vae_err('vae_video_out', f'x must be [T, H, W, C] and out [C, T_total, H, W], got {tuple(x.shape)} and {tuple(out.shape)}')
     T, H, W, C = x.shape
-    lib.call('mg_vae_video_out_f32', _p(x), C, T, H, W, _p(out), int(t_off), out.shape[1], _st())
+    t_off = int(t_off)
+    if (out.shape[0], out.shape[2], out.shape[3]) != (C, H, W) or t_off < 0 or t_off + T > out.shape[1]:
+        _vae_err('vae_video_out', f'frames [{t_off}, {t_off} + {T}) of x {tuple(x.shape)} do not fit out {tuple(out.shape)}')
+    lib.call('mg_vae_video_out_f32', _p(x), C, T, H, W, _p(out), t_off, out.shape[1], _st())
     return out
 
 
 def vae_time_interleave(x, out):
+    """x [T,H,W,2C] -> out [2T,H,W,C]: frame 2t from channels [0, C), frame 2t + 1 from [C, 2C)."""
+    _chk_flat(x, torch.float32, 'vae_time_interleave: x')
+    _chk_flat(out, torch.float32, 'vae_time_interleave: out')
+    if x.dim() != 4 or x.shape[3] % 2 or x.shape[3] == 0:
+        _vae_err('vae_time_interleave', f'x must be [T, H, W, 2C], got {tuple(x.shape)}')
     T, H, W, C2 = x.shape
+    if tuple(out.shape) != (2 * T, H, W, C2 // 2):
+        _vae_err('vae_time_interleave', f'out must be {(2 * T, H, W, C2 // 2)}, got {tuple(out.shape)}')
     lib.call('mg_vae_time_interleave_f32', _p(x), T, H * W, C2 // 2, _p(out), _st())
     return out
 
