@@ -15,23 +15,16 @@ import torch.distributed as dist
 
 from ..backend import ops
 from . import collectives
+from .layout import SpLayout
 
 
 def enable_ring_attention(model, group=None):
     """shard the token axis of `model` over `group` with ring attention instead of Ulysses."""
     if not dist.is_initialized():
         raise RuntimeError('torch.distributed is not initialised (launch with torchrun, one process per GPU)')
-    if model.dim // model.num_heads != 128:
+    if model.dim // model.num_heads != 128:     # also on a group of one rank, where the layout itself has no ring to refuse
         raise NotImplementedError('ring attention is built on the head_dim 128 kernels')
-    model.sp_group = group if group is not None else dist.group.WORLD
-    model.sp_size = dist.get_world_size(group)
-    model.sp_rank = dist.get_rank(group)
-    model.ring = True
-    model.uly_group, model.uly_size, model.ring_group, model.ring_size = None, None, None, None
-    model._ws = {}
-    from .xdit_context_parallel import tag_attention_modules
-    tag_attention_modules(model)        # the stand-alone self-attention operator then refuses the ring layout instead of
-    return model                        # silently running Ulysses over WORLD
+    return model.set_sp_layout(SpLayout.ring(group))
 
 
 def enable_hybrid_sp(model, ulysses_size, ring_size, group=None):
@@ -40,26 +33,7 @@ def enable_hybrid_sp(model, ulysses_size, ring_size, group=None):
     ranks {u, u+U, u+2U, ...} form the ring that rotates the K/V blocks of the groups.  Needs heads % U == 0."""
     if not dist.is_initialized():
         raise RuntimeError('torch.distributed is not initialised (launch with torchrun, one process per GPU)')
-    P, rank = dist.get_world_size(group), dist.get_rank(group)
-    U, R = int(ulysses_size), int(ring_size)
-    if U * R != P:
-        raise ValueError('The number of ulysses_size and ring_size should be equal to the world size.')
-    if model.num_heads % U:
-        raise ValueError(f'`num_heads` {model.num_heads} cannot be divided evenly by the ulysses size {U}')
-    if R > 1 and model.dim // model.num_heads != 128:
-        raise NotImplementedError('ring attention is built on the head_dim 128 kernels')
-    glob = (lambda r: dist.get_global_rank(group, r)) if group is not None else (lambda r: r)
-    uly_groups = [dist.new_group([glob(g * U + u) for u in range(U)]) for g in range(R)]     # every rank creates every group
-    ring_groups = [dist.new_group([glob(u + g * U) for g in range(R)]) for u in range(U)]
-    model.sp_group = group if group is not None else dist.group.WORLD
-    model.sp_size, model.sp_rank = P, rank
-    model.uly_group, model.uly_size = uly_groups[rank // U], U
-    model.ring_group, model.ring_size, model.ring_rank = ring_groups[rank % U], R, rank // U
-    model.ring = R > 1
-    model._ws = {}
-    from .xdit_context_parallel import tag_attention_modules
-    tag_attention_modules(model)
-    return model
+    return model.set_sp_layout(SpLayout.hybrid(ulysses_size, ring_size, group))
 
 
 def ring_attention(q, k, v, out, ws, group, P, rank, heads, scale, prescaled=False):

@@ -36,6 +36,7 @@ import torch
 import torch.nn as nn
 
 from ..backend import ops
+from ..distributed.layout import SpLayout
 from .attention import attend, pack_tiles, q_prescale
 from .attention import flash_attention      # operator seam (1): the reference binds it here by name (model.py:10)
 
@@ -76,6 +77,7 @@ class _Attn(nn.Module):
     """parameters of WanSelfAttention / WanT2VCrossAttention (reference model.py:102-181).  Inside WanModel.forward
     attention runs fused in the engine's layer loop; `forward` below is the same operator stand-alone, with the
     reference's call shape — the operator seam of text2video.py:97-100 (`types.MethodType(fn, block.self_attn)`)."""
+    sp = None       # a self-attention module's tag: the model's SpLayout where its Ulysses exchange is on (WanModel.set_sp_layout)
 
     def __init__(self, dim, device, num_heads=None, eps=1e-6):
         super().__init__()
@@ -89,16 +91,15 @@ class _Attn(nn.Module):
     def forward(self, x, seq_lens, grid_sizes, freqs=None, sp=None):
         """WanSelfAttention.forward (model.py:127-156): x [B, L, C] -> [B, L, C] bf16.  `freqs` (the reference's
         complex table) is accepted and ignored: the rotation angles are rebuilt from grid_sizes (same formula).
-        sp = (group, size, rank in the group, rank of the token shard): x is the rank's token shard, Ulysses exchange
-        around the attention (usp_attn_forward, xdit_context_parallel.py:155-198)."""
-        if sp == 'ring':
+        sp = an SpLayout (wan/distributed/layout.py): x is the rank's token shard, Ulysses exchange around the attention
+        (usp_attn_forward, xdit_context_parallel.py:155-198)."""
+        if sp is not None and sp.R > 1:
             raise NotImplementedError('the stand-alone self-attention operator does not rotate K/V blocks: under the ring / '
                                       'hybrid layouts call WanModel.forward (wan/distributed/ring.py)')
         d, N = self.dim, self.num_heads
         hd = d // N
         bf = torch.bfloat16
-        P = sp[1] if sp else 1
-        pos_rank = (sp[3] if len(sp) > 3 else sp[2]) if sp else 0
+        P, pos_rank = (sp.U, sp.rank) if sp is not None else (1, 0)
         outs = []
         for b in range(x.shape[0]):
             h = x[b].to(bf).contiguous()
@@ -110,7 +111,7 @@ class _Attn(nn.Module):
             # from here on the pieces of the fused layer loop (WanModel._self_attention): the same launches, the same bits
             self.norm_rope_qk(q, k, qn, kn, rope_cos_sin(hd, grid).to(dev), grid, pos_rank * L)
             if P > 1:
-                self._exchange(sp[0], P, L, dev).run(qn, kn, v, a, lambda qg, kg, vg, ag, n: attend(qg, kg, vg, ag, kg.shape[0], n, hd))
+                self._exchange(sp.uly_group, P, L, dev).run(qn, kn, v, a, lambda qg, kg, vg, ag, n: attend(qg, kg, vg, ag, kg.shape[0], n, hd))
             else:
                 attend(qn, kn, v, a, min(L, int(seq_lens[b])) if seq_lens is not None else L, N, hd)
             ops.gemm(a, self.o.weight, self.o.bias, ops.BIAS_BF16, o)
@@ -296,17 +297,14 @@ class WanModel(nn.Module):
         self.time_projection = nn.ModuleDict({'1': _Lin(6 * dim, dim, torch.float32, dv)})
         self.blocks = nn.ModuleList([_Block(dim, ffn_dim, dv, num_heads, eps) for _ in range(num_layers)])
         self.head = _Head(dim, math.prod(self.patch_size) * out_dim, dv)
-        # sequence-parallel placement, installed by wan.distributed (Ulysses); 1 = single GPU
-        self.sp_size, self.sp_rank, self.sp_group = 1, 0, None
+        # sequence-parallel placement: one value, written by set_sp_layout alone (sp_size / sp_rank / sp_group read it).  The attention
+        # modules' tags are not written here: a never-configured module is what usp_attn_forward's default recognises
+        self.sp_layout = SpLayout.single()
         self.sp_force = False   # run the Ulysses collectives even on a 1-rank group (RCCL smoke test)
         # training-side SP forward (scripts/train/model/model_seq.py): the sequence is zero-padded to seq_len before it
         # is chunked over the ranks and padded keys are masked (k_lens); cross-attention is head-sharded
         self.sp_mask_padded_keys = False
         self.cross_attn_head_sharded = False
-        self.ring = False       # sequence parallelism by ring attention instead of Ulysses (wan/distributed/ring.py)
-        # hybrid layout (wan/distributed/ring.py: enable_hybrid_sp): Ulysses inside groups of `uly_size` consecutive
-        # ranks, ring attention across the `ring_size` groups; None = derive from sp_size / ring
-        self.uly_group, self.uly_size, self.ring_group, self.ring_size, self.ring_rank = None, None, None, None, 0
         self._packed = None
         self._shards = None             # wan.distributed.fsdp.BlockShards installs itself here: the GEMM weights are block-sharded
         self._freqs = None              # the reference's complex RoPE table, built by the `freqs` property
@@ -320,6 +318,23 @@ class WanModel(nn.Module):
         self._lora_base = None          # ... and the touched weights as they were (keep_base=True), for unload_lora
         self._step_mode = None          # step_cache(): ('compute' | 'skip', stats) while the scope is open
         self.step_cache_stats = {}      # stats=True: context key -> (sum |r_new - r_old|, sum |r_old|) of its last computed step
+
+    sp_size = property(lambda self: self.sp_layout.size)
+    sp_rank = property(lambda self: self.sp_layout.rank)
+    sp_group = property(lambda self: self.sp_layout.group)
+
+    def set_sp_layout(self, layout):
+        """the one writer of the sequence-parallel placement (an SpLayout, wan/distributed/layout.py): checks it against the heads, drops the
+        old layout's workspace and tags every self-attention module for its stand-alone operator (usp_attn_forward)"""
+        if self.num_heads % layout.U:       # reference generate.py:238-239
+            raise ValueError(f'`num_heads` {self.num_heads} cannot be divided evenly by the '
+                             f'{"sequence-parallel" if layout.R == 1 else "ulysses"} size {layout.U}')
+        if layout.R > 1 and self.dim // self.num_heads != 128:
+            raise NotImplementedError('ring attention is built on the head_dim 128 kernels')
+        self.sp_layout, self._ws = layout, {}
+        for blk in self.blocks:     # one rank: no exchange.  A ring / hybrid tag makes the operator refuse: only the fused forward rotates K/V blocks
+            blk.self_attn.sp = layout if layout.size > 1 else None
+        return self
 
     @property
     def freqs(self):
@@ -623,14 +638,9 @@ class WanModel(nn.Module):
             return lw
         return {**lw, **sh.fetch(i)}
 
-    def _sp_layout(self):
-        """(U, R): Ulysses degree inside a group, ring degree across groups; U * R == sp_size."""
-        if self.uly_size is not None:
-            return self.uly_size, self.ring_size
-        return (1, self.sp_size) if self.ring else (self.sp_size, 1)
-
     def _workspace(self, L, dev):
-        key = (L, str(dev), self.sp_force, self.sp_size, self._sp_layout())
+        lay = self.sp_layout
+        key = (L, str(dev), self.sp_force, lay)
         ws = self._ws.get(key)
         if ws is None:
             d, f = self.dim, self.ffn_dim
@@ -642,13 +652,12 @@ class WanModel(nn.Module):
                       hf=e(L, d, dt=f32), y=e(L, math.prod(self.patch_size) * self.out_dim, dt=f32),
                       sin=e(1, self.freq_dim, dt=f32), e1=e(d, dt=f32), e=e(d, dt=f32), e0=e(6, d, dt=f32),
                       mod=e(6 * self.num_layers, d, dt=f32), hmod=e(2, d, dt=f32))
-            U, R = self._sp_layout()
+            U, R = lay.U, lay.R
             n_loc, Lg = self.num_heads // U, L * U          # heads and tokens a rank attends after the Ulysses exchange
             n_att = n_loc
             if U > 1 or self.sp_force:     # pipelined packed exchange (wan/distributed/ulysses.py): buffers live there
                 from ..distributed.ulysses import HeadExchange
-                ug = self.uly_group if self.uly_group is not None else self.sp_group
-                ws['xchg'] = HeadExchange(ug, U, self.num_heads, hd, L, dev, max_groups=1 if R > 1 else None)
+                ws['xchg'] = HeadExchange(lay.uly_group, U, self.num_heads, hd, L, dev, max_groups=1 if R > 1 else None)
                 n_att = max(n for _, n in ws['xchg'].groups)
             if hd == 128 and R == 1:   # K / V packed into 64-key tiles (operand layout of the MFMA attention kernel)
                 n_pk = ops.packed_kv_numel(Lg, n_att)
@@ -719,7 +728,8 @@ class WanModel(nn.Module):
         ws, L = plan.ws, plan.L
         qkv = ws['qkv']
         q, k, v, a = ws['q'], ws['k'], qkv[:, 2 * d:], ws['a']
-        fa = plan.fa if self.sp_size == 1 and not self.sp_force else None
+        lay = self.sp_layout
+        fa = plan.fa if lay.size == 1 and not self.sp_force else None
         blk.self_attn.norm_rope_qk(qkv[:, :d], qkv[:, d:2 * d], q, k, plan.rope, plan.grid, plan.pos0, prescale=fa is None)
         if fa is not None:
             # operator seam (1): the caller's function gets the reference's call (model.py:146-151): q, k roped
@@ -728,7 +738,7 @@ class WanModel(nn.Module):
                    k_lens=torch.tensor([plan.Lfull]), window_size=self.window_size)
             a.copy_(y.reshape(L, d))
             return
-        U, R = self._sp_layout()
+        U, R = lay.U, lay.R
         tiles = (ws['kp'], ws['vp']) if 'kp' in ws else None
         # while an exchange is in flight the persistent attention grid leaves `reserve_cus` CUs to RCCL's kernels
         reserve = ws['xchg'].reserve_cus if 'xchg' in ws else 0
@@ -736,9 +746,7 @@ class WanModel(nn.Module):
         def attn(qg, kg, vg, ag, heads):        # operands may be strided column views; ag contiguous
             if R > 1:                           # ring attention across the groups (hd 128 only)
                 from ..distributed.ring import ring_attention
-                rg = self.ring_group if self.ring_group is not None else self.sp_group
-                rr = self.ring_rank if self.uly_size is not None else self.sp_rank
-                ring_attention(qg, kg, vg, ag, ws, rg, R, rr, heads, 1.0 / math.sqrt(hd), prescaled=True)
+                ring_attention(qg, kg, vg, ag, ws, lay.ring_group, R, lay.ring_rank, heads, 1.0 / math.sqrt(hd), prescaled=True)
             else:                               # keys past the video's tokens are padding (k_lens)
                 attend(qg, kg, vg, ag, min(kg.shape[0], plan.Lfull), heads, hd, tiles=tiles, reserve_cus=reserve)
 
@@ -790,7 +798,7 @@ class WanModel(nn.Module):
             # context_lens = None for T2V
             y = fa(ws['k'].view(1, plan.L, N, hd), kc.view(1, -1, N, hd), vc.reshape(1, -1, N, hd), k_lens=None)
             ws['a'].copy_(y.reshape(plan.L, self.dim))
-        elif self.cross_attn_head_sharded and self.sp_size > 1:
+        elif self.cross_attn_head_sharded and self.sp_layout.size > 1:
             self._cross_attention_head_sharded(ws, kc, vc)
         else:
             attend(ws['k'], kc, vc, ws['a'], self.text_len, N, hd, packed=True)
@@ -800,9 +808,7 @@ class WanModel(nn.Module):
         """model_seq.py:271-294: q through the seq->head all-to-all, K/V narrowed to this rank's heads (shrink_head),
         attention over ALL tokens x local heads, head->seq all-to-all back.  Same values as the token-local form."""
         from ..distributed import ulysses
-        U = self._sp_layout()[0]
-        ug = self.uly_group if self.uly_group is not None else self.sp_group
-        ur = self.sp_rank % U
+        U, ug, ur = self.sp_layout.U, self.sp_layout.uly_group, self.sp_layout.uly_rank
         N, hd = self.num_heads, self.dim // self.num_heads
         nl, L = N // U, ws['k'].shape[0]
         qg = torch.empty(L * U, nl * hd, dtype=torch.bfloat16, device=ws['k'].device)
@@ -825,20 +831,21 @@ class WanModel(nn.Module):
         grid = (F, H // ph, W // pw)
         Lfull = grid[0] * grid[1] * grid[2]
         assert Lfull <= seq_len, 'seq_lens.max() <= seq_len (reference model.py:534)'
-        P = self.sp_size
+        lay = self.sp_layout
+        P = lay.size
         Ltot = Lfull
         if P > 1 and self.sp_mask_padded_keys:
             # model_seq.py:704-706,757: pad to seq_len, chunk; padded keys masked through k_lens (:247-252)
-            assert seq_len % P == 0 and self.num_heads % self._sp_layout()[0] == 0 and self._sp_layout()[1] == 1, \
+            assert seq_len % P == 0 and self.num_heads % lay.U == 0 and lay.R == 1, \
                 'training-side sequence parallel needs seq_len % sp == 0, heads % sp == 0 (Ulysses only)'
             Ltot = seq_len
         elif P > 1:
             # reference SP path does not mask padded keys (xdit_context_parallel.py:178-193): it is
             # only correct without padding, which is what every supported size gives
-            assert seq_len == Lfull and Lfull % P == 0 and self.num_heads % self._sp_layout()[0] == 0, \
+            assert seq_len == Lfull and Lfull % P == 0 and self.num_heads % lay.U == 0, \
                 'sequence parallel needs L % sp == 0, heads % sp == 0 and no padding'
         L = Ltot // P
-        pos0 = self.sp_rank * L
+        pos0 = lay.rank * L
         n_valid = min(max(Lfull - pos0, 0), L)
         return _Plan((F, H, W), grid, Lfull, L, pos0, n_valid, self._workspace(L, lat.device), self._rope_tab(grid, lat.device),
                      _rebound_flash_attention())
@@ -849,7 +856,7 @@ class WanModel(nn.Module):
         ws, x, n_valid = plan.ws, plan.ws['x'], plan.n_valid
         if patches:
             _, ph, pw = self.patch_size
-            if self.sp_size == 1:
+            if self.sp_layout.size == 1:
                 ops.patchify(lat, ph, pw, ws['tok'])
             else:
                 full = torch.empty(plan.Lfull, ws['tok'].shape[1], dtype=torch.bfloat16, device=lat.device)
@@ -930,12 +937,12 @@ class WanModel(nn.Module):
 
     def _head_out(self, ws, grid, fhw, dev):
         """head Linear on ws['hf'], the SP all-gather and unpatchify (model.py:342, :561-565)"""
-        P = self.sp_size
+        lay = self.sp_layout
         ops.head_gemm(ws['hf'], self.head.head.weight, self.head.head.bias, ws['y'])
         y = ws['y']
-        if P > 1:
+        if lay.size > 1:
             from ..distributed import ulysses
-            y = ulysses.all_gather_seq(ws['y'], self.sp_group, P)                   # get_sp_group().all_gather
+            y = ulysses.all_gather_seq(ws['y'], lay.group, lay.size)                  # get_sp_group().all_gather
         out = torch.empty(self.out_dim, *fhw, dtype=torch.float32, device=dev)
         ops.unpatchify(y, self.out_dim, grid[0], grid[1], grid[2], self.patch_size[1], self.patch_size[2], out)
         return out

@@ -88,7 +88,8 @@ class WanT2V:
         # vae_parallel: True / 'spatial' = every rank decodes its band of image columns (WanVAE.decode_spatial); 'pipeline' = the layer pipeline
         self.vae_parallel_kind = vae_parallel if vae_parallel in ('spatial', 'pipeline') else 'spatial'
         # flag combinations are validated BEFORE any process group is created
-        want_ring = bool(use_ring or (sp_degrees and sp_degrees[1] > 1))
+        U, R = sp_degrees or (1, 1)                                 # the reference CLI's (ulysses_size, ring_size)
+        want_ring = bool(use_ring or R > 1)
         if cfg_parallel and want_ring:
             raise NotImplementedError('cfg_parallel is built on plain Ulysses groups (no ring / hybrid layout)')
         if cfg_parallel and not (dist.is_initialized() and dist.get_world_size() % 2 == 0):
@@ -100,18 +101,15 @@ class WanT2V:
             # (wan/distributed/cfg_parallel.py) — independent of use_usp: 2 ranks need no sequence parallelism at all
             from .distributed.cfg_parallel import enable_cfg_parallel
             self.cfgp = enable_cfg_parallel(self.model)
-        elif use_usp and (use_ring or sp_degrees):
+        elif use_usp:
             from .distributed.ring import enable_hybrid_sp, enable_ring_attention
-            if sp_degrees and sp_degrees[0] > 1 and sp_degrees[1] > 1:      # (ulysses_size, ring_size)
-                enable_hybrid_sp(self.model, *sp_degrees)
+            from .distributed.xdit_context_parallel import enable_sequence_parallel
+            if U > 1 and R > 1:
+                enable_hybrid_sp(self.model, U, R)
             elif want_ring:
                 enable_ring_attention(self.model)
             else:
-                from .distributed.xdit_context_parallel import enable_sequence_parallel
                 enable_sequence_parallel(self.model)
-        elif use_usp:
-            from .distributed.xdit_context_parallel import enable_sequence_parallel
-            enable_sequence_parallel(self.model)
         self.sp_size = self.model.sp_size
         if dit_fsdp:
             from .distributed.fsdp import shard_model

@@ -34,6 +34,7 @@ _PKG = os.path.join(_ROOT, 'moviigen1.1_amd')
 if _PKG not in sys.path:
     sys.path.insert(0, _PKG)
 
+from wan.distributed.layout import SpLayout  # noqa: E402
 from wan.distributed.xdit_context_parallel import enable_sequence_parallel  # noqa: E402
 from wan.modules.model import WanModel as _EngineWanModel  # noqa: E402
 
@@ -83,10 +84,7 @@ class WanModel(_EngineWanModel):
         if want > 1 and (self.sp_size != want or self.sp_group is not nccl_info.group):
             enable_sequence_parallel(self, nccl_info.group)
         elif want == 1 and self.sp_size != 1:
-            self.sp_size, self.sp_rank, self.sp_group = 1, 0, None
-            self._ws = {}
-            for blk in self.blocks:
-                blk.self_attn.sp = None
+            self.set_sp_layout(SpLayout.single())
         self.sp_mask_padded_keys = True        # pad to seq_len, chunk, mask the padded keys (:704-706, :757, :247-252)
         self.cross_attn_head_sharded = True    # :271-294
 

@@ -13,6 +13,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, 'moviigen1.1_amd'), os.path.join(ROOT, 
 import weights as W  # noqa: E402
 import wan  # noqa: E402
 from wan.backend import ops  # noqa: E402
+from wan.distributed.layout import SpLayout  # noqa: E402
 from wan.distributed.ring import enable_ring_attention, ring_attention  # noqa: E402
 
 dist.init_process_group('gloo')
@@ -56,20 +57,31 @@ t = torch.tensor([650], device=dev)
 Lm = 3 * 4 * 8
 single = m([lat], t=t, context=[ctx], seq_len=Lm)[0].clone()
 enable_ring_attention(m)
-assert m.sp_size == P and m.ring
+assert m.sp_size == P and m.sp_layout.R == P and m.sp_layout.U == 1
 got = m([lat], t=t, context=[ctx], seq_len=Lm)[0]
 rel = ((got - single).norm() / single.norm()).item()
 assert rel < 5e-3, rel
 print(f'RING_MODEL_OK rank{rank}/{P} rel {rel:.2e}', flush=True)
 
+
+def back_to_single(leg):
+    """the single layout after `leg`: nothing of the old placement is left, so the first forward's launches run again, bit for bit"""
+    m.set_sp_layout(SpLayout.single())
+    assert torch.equal(m([lat], t=t, context=[ctx], seq_len=Lm)[0], single)
+    print(f'{leg}_RESET_OK rank{rank}/{P}', flush=True)
+
+
+back_to_single('RING')
+
 # ---- hybrid: Ulysses 2 x ring P/2 (the reference CLI's --ulysses_size 2 --ring_size P/2) ---------------------
 if P % 2 == 0 and P >= 4:
     from wan.distributed.ring import enable_hybrid_sp
     enable_hybrid_sp(m, 2, P // 2)
-    assert m._sp_layout() == (2, P // 2) and m.sp_size == P
+    assert (m.sp_layout.U, m.sp_layout.R) == (2, P // 2) and m.sp_size == P
     got = m([lat], t=t, context=[ctx], seq_len=Lm)[0]
     rel = ((got - single).norm() / single.norm()).item()
     assert rel < 5e-3, rel
     print(f'HYBRID_OK rank{rank}/{P} rel {rel:.2e}', flush=True)
+    back_to_single('HYBRID')
 dist.barrier()
 dist.destroy_process_group()

@@ -1731,6 +1731,8 @@ def test_ring_attention_one_gpu(world):
     for k in range(world):
         assert f'RING_OP_OK rank{k}/{world}' in r.stdout and f'RING_MODEL_OK rank{k}/{world}' in r.stdout
         assert world != 4 or f'HYBRID_OK rank{k}/{world}' in r.stdout
+        # back on SpLayout.single() after each leg, the forward is the first one's again, bit for bit
+        assert f'RING_RESET_OK rank{k}/{world}' in r.stdout and (world != 4 or f'HYBRID_RESET_OK rank{k}/{world}' in r.stdout)
 
 
 def test_attention_lse_and_merge(dev):

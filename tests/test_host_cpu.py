@@ -587,6 +587,118 @@ def test_sp_group_chooser_on_the_baseline_shapes():
     assert [n for _, n in split_heads(10, 4)] == [3, 3, 2, 2]
 
 
+# ---- sequence-parallel placement as one value (wan/distributed/layout.py: SpLayout, WanModel.set_sp_layout) ----
+_LAYOUT_FIELDS = ('group', 'size', 'rank', 'U', 'uly_group', 'uly_rank', 'R', 'ring_group', 'ring_rank')
+_SINGLE = (None, 1, 0, 1, None, 0, 1, None, 0)
+
+
+def _layout_fields(lay):
+    return tuple(getattr(lay, f) for f in _LAYOUT_FIELDS)
+
+
+def _stub_hybrid_layout():
+    """size 4 = Ulysses 2 x ring 2, rank 3, on stub group objects: the constructor calls nothing in torch.distributed"""
+    from wan.distributed.layout import SpLayout
+    g, ug, rg = object(), object(), object()
+    return SpLayout(group=g, size=4, rank=3, U=2, uly_group=ug, uly_rank=1, R=2, ring_group=rg, ring_rank=1)
+
+
+def _assert_single(m):
+    assert _layout_fields(m.sp_layout) == _SINGLE and (m.sp_size, m.sp_rank, m.sp_group) == (1, 0, None)
+    assert len(m.blocks) > 0 and all(blk.self_attn.sp is None for blk in m.blocks)
+
+
+def test_hybrid_rank_lists_partition_the_ranks():
+    from wan.distributed.layout import hybrid_rank_lists
+    for P in range(1, 9):
+        for U in (u for u in range(1, P + 1) if P % u == 0):
+            R = P // U
+            uly, ring = hybrid_rank_lists(P, U)
+            assert uly == [list(range(g * U, (g + 1) * U)) for g in range(R)]           # R runs of U consecutive ranks
+            assert ring == [list(range(u, P, U)) for u in range(U)]                     # U strided lists of R ranks
+            for lists in (uly, ring):
+                assert sorted(r for lst in lists for r in lst) == list(range(P))        # a partition of range(P)
+            for r in range(P):
+                assert uly[r // U][r % U] == r and ring[r % U][r // U] == r
+
+
+def test_sp_layout_constructor_refuses_inconsistent_fields():
+    from wan.distributed.layout import SpLayout
+    g, ug, rg = object(), object(), object()
+    ok = dict(group=g, size=4, rank=3, U=2, uly_group=ug, uly_rank=1, R=2, ring_group=rg, ring_rank=1)
+    assert _layout_fields(SpLayout(**ok)) == tuple(ok[f] for f in _LAYOUT_FIELDS)
+    assert _layout_fields(SpLayout.single()) == _SINGLE
+    bad = [dict(ok, R=3), dict(ok, U=4), dict(ok, uly_rank=0), dict(ok, ring_rank=0), dict(ok, rank=4, uly_rank=0, ring_rank=2),
+           dict(ok, U=4, R=1, uly_rank=3, ring_rank=0),                     # U == size with a uly_group that is not group
+           dict(ok, U=1, R=4, uly_rank=0, ring_rank=3),                     # R == size with a ring_group that is not group
+           dict(ok, uly_group=None), dict(ok, ring_group=None), dict(ok, group=None)]
+    for kw in bad:
+        with pytest.raises(ValueError):
+            SpLayout(**kw)
+    SpLayout(**dict(ok, U=4, R=1, uly_group=g, uly_rank=3, ring_group=None, ring_rank=0))
+    lay = SpLayout(**ok)
+    with pytest.raises(AttributeError):                                     # immutable
+        lay.U = 4
+
+
+def test_fresh_wan_model_is_single():
+    import wan
+    _assert_single(wan.modules.WanModel(**W.TINY_DIT))
+
+
+def test_set_sp_layout_installs_and_resets():
+    """the stale-state case: a model that ran under a hybrid layout and is put back to one rank keeps nothing of the old degrees"""
+    import wan
+    from wan.distributed.layout import SpLayout
+    m = wan.modules.WanModel(**W.SMALL_DIT_HD128)
+    assert (m.dim // m.num_heads, m.num_heads % 2) == (128, 0)
+    fresh = set(vars(m))
+    lay = _stub_hybrid_layout()
+    m._ws['sentinel'] = object()
+    assert m.set_sp_layout(lay) is m
+    assert m.sp_layout is lay and (m.sp_size, m.sp_rank, m.sp_group) == (4, 3, lay.group) and m._ws == {}
+    assert all(blk.self_attn.sp is lay for blk in m.blocks)
+    m._ws['sentinel'] = object()
+    m.set_sp_layout(SpLayout.single())
+    _assert_single(m)
+    assert (m.sp_layout.U, m.sp_layout.R) == (1, 1) and m._ws == {}
+    assert set(vars(m)) == fresh                                            # no attribute appeared on the way ...
+    stale = (lay, lay.group, lay.uly_group, lay.ring_group)
+    for name, val in vars(m).items():                                       # ... and none still holds the old layout or a group of it
+        assert not any(val is s for s in stale), name
+    for name in ('ring', 'uly_size', 'uly_group', 'ring_size', 'ring_group', 'ring_rank', '_sp_layout'):
+        assert not hasattr(m, name), name
+    for name in ('sp_size', 'sp_rank', 'sp_group'):
+        with pytest.raises(AttributeError):
+            setattr(m, name, 2)
+
+
+def test_set_sp_layout_validates_like_the_entry_points():
+    import wan
+    from wan.distributed.layout import SpLayout
+    g = object()
+    m = wan.modules.WanModel(**W.TINY_DIT)
+    U = next(u for u in range(2, m.num_heads + 2) if m.num_heads % u)
+    with pytest.raises(ValueError, match='cannot be divided evenly'):
+        m.set_sp_layout(SpLayout(group=g, size=U, rank=0, U=U, uly_group=g, uly_rank=0, R=1, ring_group=None, ring_rank=0))
+    assert m.dim // m.num_heads != 128
+    with pytest.raises(NotImplementedError, match='ring attention is built on the head_dim 128 kernels'):
+        m.set_sp_layout(SpLayout(group=g, size=2, rank=1, U=1, uly_group=None, uly_rank=0, R=2, ring_group=g, ring_rank=1))
+    _assert_single(m)                                                       # a refused layout changes nothing
+
+
+def test_model_seq_configure_resets_to_single():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('model_seq', os.path.join(ROOT, 'scripts', 'train', 'model', 'model_seq.py'))
+    ms = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ms)
+    m = ms.WanModel(**W.SMALL_DIT_HD128)
+    m.set_sp_layout(_stub_hybrid_layout())
+    assert not ms.get_sequence_parallel_state() and m.sp_size == 4
+    m._configure()
+    _assert_single(m)
+
+
 def test_mp4_mjpeg_container(tmp_path):
     """wan/utils/mp4_mjpeg.py — what `cache_video` writes when imageio is absent (reference wan/utils/utils.py:23-60 hands the frames to
     imageio / libx264).  The file must be a well-formed ISO base media file: ftyp | mdat | moov in that order, every box size exact, the one chunk

@@ -29,6 +29,7 @@ from wan.backend import ops  # noqa: E402
 from wan.distributed._test_transport import EmulatedGroup  # noqa: E402
 from wan.distributed.cfg_parallel import CfgParallel  # noqa: E402
 from wan.distributed.fsdp import BlockShards  # noqa: E402
+from wan.distributed.layout import SpLayout  # noqa: E402
 from wan.distributed.ulysses import HeadExchange  # noqa: E402
 from wan.distributed.xdit_context_parallel import enable_sequence_parallel  # noqa: E402
 from wan.utils.fm_solvers_unipc import FlowUniPCMultistepScheduler  # noqa: E402
@@ -119,7 +120,7 @@ def main():
             if half > 1:
                 enable_sequence_parallel(model, group=groups['sp'])
             else:
-                model.sp_size, model.sp_rank, model.sp_group, model._ws = 1, 0, None, {}
+                model.set_sp_layout(SpLayout.single())
             cfgp = CfgParallel(0, groups['pair'], groups['sp'], half)
         else:
             groups['sp'] = EmulatedGroup(P, 0, f'ulysses {P}')
