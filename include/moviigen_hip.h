@@ -334,6 +334,33 @@ int mg_lincomb4_f32(float* out, int64_t n, const float* x0, float c0, const floa
 int mg_cfg_combine_f32(float* out, const float* uncond, const float* cond, float guide_scale,
                        int64_t n, void* stream);
 
+/* Guidance options (not the reference's arithmetic, opt-in): CFG-Zero* and guidance rescale as three launches
+ * behind the pair of predictions of a guided step.  None of them reads on the host, allocates or keeps state: capturable.
+ *
+ * mg_cfg_stats_f32: stats[5] = (sum u, sum c, sum u^2, sum c^2, sum u c) over the n elements of uncond (u) and cond (c).  Every
+ * element is widened to fp64 and multiplied there (the product of two fp32 values is exact in fp64): only the additions round.
+ * The grid is fixed, a lane's elements and their order are a function of n alone, the per-workgroup sums go to `partials`
+ * (mg_cfg_stats_partials_bytes() bytes OWNED BY THE CALLER, no initial value needed) and a second launch adds them in index
+ * order: the same inputs give the same 40 bytes, no atomics.  The inputs are only read.
+ *   n >= 1, any value (scalar tail).  uncond, cond 16-byte aligned, stats, partials 8-byte aligned: else MG_ERR_SHAPE.
+ *
+ * mg_cfg_coef_f32: coef[2] = (a_u, a_c), the coefficients of the guided prediction p = a_u u + a_c c, from stats: one lane,
+ * every operation in fp64 without contraction, one rounding to fp32.
+ *   s = zero_star ? S_uc / (S_uu + 1e-8) : 1            (CFG-Zero*: the projection of c on u)
+ *   a_u = s (1 - g), a_c = g                            (= s u + g (c - s u))
+ *   rescale > 0:  mean_p = (a_u S_u + a_c S_c) / n,  E[p^2] = (a_u^2 S_uu + 2 a_u a_c S_uc + a_c^2 S_cc) / n,
+ *                 var_p = E[p^2] - mean_p^2,  var_c = S_cc / n - (S_c / n)^2,
+ *                 f = rescale sqrt(var_c / var_p) + (1 - rescale), f = 1 when var_p <= 0 or var_c < 0;  a_u, a_c *= f
+ *   g finite and rescale in [0, 1]: else MG_ERR_ARG.  n >= 1 (the n of mg_cfg_stats_f32).
+ *
+ * mg_cfg_combine_coef_f32: out[i] = fma(a_c, cond[i], a_u uncond[i]) with (a_u, a_c) = coef[0..1] read from DEVICE memory:
+ * the bits of mg_lincomb4_f32(out, n, uncond, a_u, cond, a_c, ...).  out may be uncond or cond.
+ *   n >= 0.  out, uncond, cond 16-byte aligned: else MG_ERR_SHAPE. */
+int64_t mg_cfg_stats_partials_bytes(void);
+int mg_cfg_stats_f32(const float* uncond, const float* cond, int64_t n, double* stats, double* partials, void* stream);
+int mg_cfg_coef_f32(const double* stats, int64_t n, float g, int zero_star, float rescale, float* coef, void* stream);
+int mg_cfg_combine_coef_f32(float* out, const float* uncond, const float* cond, int64_t n, const float* coef, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * umT5 text encoder glue (the GEMMs are mg_gemm_bf16, the T5LayerNorm is
  * mg_rmsnorm_rope_bf16 without RoPE).  Reference wan/modules/t5.py, model in bf16.

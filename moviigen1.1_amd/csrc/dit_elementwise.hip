@@ -836,5 +836,161 @@ extern "C" int mg_step_resid_capture_f32(float* r, const float* x, const float* 
     return mg_check_launch();
 }
 
+// ---------------------------------------------------------------------------------------------
+// guidance options: CFG-Zero* and guidance rescale need five whole-latent sums of the pair of predictions in every
+// guided step, and the mix that follows reads its two coefficients from device memory: three launches, no host read.
+//   cfg_stats: (sum u, sum c, sum u^2, sum c^2, sum u c).  Each element is widened to fp64 FIRST and multiplied in fp64: the product
+//   of two fp32 values has 48 significant bits and is exact there (so fused or not, the same bits), only the additions round.  The
+//   pattern is step_resid_capture_kernel<true>'s: CS_GRID workgroups of NT lanes whatever the device, a lane's elements and their
+//   order a function of n alone, a fixed tree within the workgroup, the partials added in index order by a second launch, no atomics.
+// ---------------------------------------------------------------------------------------------
+#define CS_GRID SR_GRID
+#define CS_UNROLL 4
+#define CS_SUMS 5
+
+__global__ __launch_bounds__(NT) void cfg_stats_kernel(const float* __restrict__ uc, const float* __restrict__ co, int64_t n,
+                                                       double* __restrict__ partials) {
+    __shared__ double red[CS_SUMS][NT / 64];
+    const int64_t nvec = n >> 2;
+    const int64_t stride = (int64_t)gridDim.x * NT;
+    double s[CS_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    auto add = [&](float uf, float cf) {
+        const double u = (double)uf, c = (double)cf;
+        s[0] += u;
+        s[1] += c;
+        s[2] += u * u;
+        s[3] += c * c;
+        s[4] += u * c;
+    };
+    for (int64_t i0 = (int64_t)blockIdx.x * NT + threadIdx.x; i0 < nvec; i0 += stride * CS_UNROLL) {
+        f32x4_t a[CS_UNROLL], b[CS_UNROLL];
+#pragma unroll
+        for (int k = 0; k < CS_UNROLL; ++k) {
+            const int64_t i = i0 + k * stride;
+            if (i < nvec) {
+                a[k] = ((const f32x4_t*)uc)[i];
+                b[k] = ((const f32x4_t*)co)[i];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < CS_UNROLL; ++k) {
+            if (i0 + k * stride < nvec) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) add(a[k][e], b[k][e]);
+            }
+        }
+    }
+    if (blockIdx.x == 0 && (int64_t)threadIdx.x < n - (nvec << 2)) {      // the scalar tail: n % 4 elements
+        const int64_t i = (nvec << 2) + threadIdx.x;
+        add(uc[i], co[i]);
+    }
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+#pragma unroll
+    for (int q = 0; q < CS_SUMS; ++q) {
+        const double t = wave_sum_f64(s[q]);
+        if (l == 0) red[q][w] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < CS_SUMS) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k < NT / 64; ++k) t += red[threadIdx.x][k];
+        partials[CS_SUMS * blockIdx.x + threadIdx.x] = t;
+    }
+}
+
+// the 40 KB of partials come in with independent loads of all NT lanes (five lanes walking them in global memory pay a memory latency
+// per step of their chains: 23.7 us measured, 15.4 us this way); lane q then adds sum q out of the LDS copy, in index order
+__global__ __launch_bounds__(NT) void cfg_stats_finish_kernel(const double* __restrict__ partials, double* __restrict__ stats) {
+    __shared__ double buf[CS_GRID * CS_SUMS];
+#pragma unroll
+    for (int i = threadIdx.x; i < CS_GRID * CS_SUMS; i += NT) buf[i] = partials[i];
+    __syncthreads();
+    if (threadIdx.x < CS_SUMS) {
+        double t = 0.0;
+#pragma unroll 8
+        for (int b = 0; b < CS_GRID; ++b) t += buf[CS_SUMS * b + threadIdx.x];
+        stats[threadIdx.x] = t;
+    }
+}
+
+extern "C" int64_t mg_cfg_stats_partials_bytes(void) { return (int64_t)CS_GRID * CS_SUMS * sizeof(double); }
+
+extern "C" int mg_cfg_stats_f32(const float* uncond, const float* cond, int64_t n, double* stats, double* partials, void* stream) {
+    if (!uncond || !cond || !stats || !partials) return MG_ERR_ARG;
+    if (n < 1) return MG_ERR_SHAPE;
+    if ((((uintptr_t)uncond | (uintptr_t)cond) & 15) || (((uintptr_t)stats | (uintptr_t)partials) & 7)) return MG_ERR_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(cfg_stats_kernel, dim3(CS_GRID), dim3(NT), 0, st, uncond, cond, n, partials);
+    hipLaunchKernelGGL(cfg_stats_finish_kernel, dim3(1), dim3(NT), 0, st, (const double*)partials, stats);
+    return mg_check_launch();
+}
+
+// the two coefficients of the guided mix a_u u + a_c c from the five sums: one lane, every operation one correctly rounded fp64
+// operation (no contraction: the value is that of the same expression anywhere), one rounding to fp32 at the end
+__global__ __launch_bounds__(64) void cfg_coef_kernel(const double* __restrict__ stats, double n, double g, int zero_star, double phi,
+                                                      float* __restrict__ coef) {
+#pragma clang fp contract(off)
+    if (threadIdx.x != 0) return;
+    const double Su = stats[0], Sc = stats[1], Suu = stats[2], Scc = stats[3], Suc = stats[4];
+    const double s = zero_star ? Suc / (Suu + 1e-8) : 1.0;      // CFG-Zero*'s projection <c, u> / (|u|^2 + 1e-8)
+    double au = s * (1.0 - g), ac = g;                           // s u + g (c - s u)
+    if (phi > 0.0) {                                             // guidance rescale: the mix pulled towards std(c) by phi
+        const double mp = (au * Su + ac * Sc) / n;
+        const double ep = (au * au * Suu + 2.0 * au * ac * Suc + ac * ac * Scc) / n;
+        const double mc = Sc / n;
+        const double varp = ep - mp * mp, varc = Scc / n - mc * mc;
+        double f = 1.0;
+        if (varp > 0.0 && varc >= 0.0) f = phi * sqrt(varc / varp) + (1.0 - phi);
+        au *= f;
+        ac *= f;
+    }
+    coef[0] = (float)au;
+    coef[1] = (float)ac;
+}
+
+extern "C" int mg_cfg_coef_f32(const double* stats, int64_t n, float g, int zero_star, float rescale, float* coef, void* stream) {
+    if (!stats || !coef) return MG_ERR_ARG;
+    if (!(g - g == 0.f) || !(rescale >= 0.f && rescale <= 1.f)) return MG_ERR_ARG;      // g finite, rescale in [0, 1] (refuses nan)
+    if (n < 1 || ((uintptr_t)stats & 7) || ((uintptr_t)coef & 3)) return MG_ERR_SHAPE;
+    hipLaunchKernelGGL(cfg_coef_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, stats, (double)n, (double)g, zero_star, (double)rescale,
+                       coef);
+    return mg_check_launch();
+}
+
+// out = a_u u + a_c c with (a_u, a_c) = coef[0..1] read from device memory: the two-term case of lincomb4_kernel written out as
+// RenoiseValue writes it, one multiply and one fused multiply-add.  A lane reads its elements before it writes them and no other
+// lane touches them: out may be u or c.
+#define CC_GRID 2048
+
+__global__ __launch_bounds__(NT) void cfg_combine_coef_kernel(float* out, const float* uc, const float* co, int64_t n,
+                                                              const float* __restrict__ coef) {
+    const float au = coef[0], ac = coef[1];
+    const int64_t nvec = n >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * NT) {
+        const f32x4_t u = ((const f32x4_t*)uc)[i], c = ((const f32x4_t*)co)[i];
+        f32x4_t v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(ac, c[e], au * u[e]);
+        ((f32x4_t*)out)[i] = v;
+    }
+    if (blockIdx.x == 0 && (int64_t)threadIdx.x < n - (nvec << 2)) {      // the scalar tail: n % 4 elements
+        const int64_t i = (nvec << 2) + threadIdx.x;
+        out[i] = __builtin_fmaf(ac, co[i], au * uc[i]);
+    }
+}
+
+extern "C" int mg_cfg_combine_coef_f32(float* out, const float* uncond, const float* cond, int64_t n, const float* coef, void* stream) {
+    if (!out || !uncond || !cond || !coef) return MG_ERR_ARG;
+    if (n < 0) return MG_ERR_SHAPE;
+    if ((((uintptr_t)out | (uintptr_t)uncond | (uintptr_t)cond) & 15) || ((uintptr_t)coef & 3)) return MG_ERR_SHAPE;
+    if (n == 0) return MG_OK;
+    int64_t grid = ((n >> 2) + NT - 1) / NT;
+    if (grid > CC_GRID) grid = CC_GRID;
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL(cfg_combine_coef_kernel, dim3((unsigned)grid), dim3(NT), 0, (hipStream_t)stream, out, uncond, cond, n, coef);
+    return mg_check_launch();
+}
+
 extern "C" const char* mg_version(void) { return "moviigen_hip 3 gfx950"; }
 extern "C" int mg_abi_version(void) { return 9; }   // 9: mg_attn_fwd_bf16_hd128 / _lse / _prescaled take a caller-owned workspace (mg_attn_workspace_bytes(); the library no longer allocates or synchronises on a launch path), + the W-band VAE entries mg_vae_conv_cols_f32 / mg_vae_upconv_phases_cols_f32 / mg_vae_attn_rows_f32; 8: the product library exports no kernel-selection switch and no profiling hook (they live in libmoviigen_hip_ab.so, -DMG_AB_BUILD; mg_*_set_variant return a status there); 7: the VAE arithmetic mode is an argument of mg_vae_conv_f32 / mg_vae_upconv_phases_f32 (mg_vae_set_mode is gone), mg_attn_w64_flag_counter counts into two words, mg_attn_fwd_bf16_hd128_prescaled gained reserve_cus; 6: + mg_vae_set_mode; 5: + mg_vae_upconv_fold_weights_f32 / mg_vae_upconv_phases_f32; 4: mg_rmsnorm_rope_bf16 gained out_scale, mg_pack_kv_bf16's K row order follows the 16x16x32 attention kernel, + mg_attn_fwd_bf16_hd128_prescaled

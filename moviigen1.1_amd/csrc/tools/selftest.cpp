@@ -613,6 +613,31 @@ static void test_small() {
         for (int64_t i = 0; i < n; ++i) err = fmax(err, fabs(o[i] - (0.5 * a[i] - 2.0 * b[i] + 3.0 * c[i])));
         report("lincomb4_f32", err, 2e-6);
     }
+    {  // guided combine: stats -> coefficients (CFG-Zero* + rescale 0.7) -> combine, against the same formulas in fp64 on the host
+        const int64_t n = 100003;
+        auto u = randf(n), c = randf(n);
+        for (int64_t i = 0; i < n; ++i) c[i] = u[i] + 0.3f * c[i];
+        Dev<float> du(u), dc(c), dout(n), dcoef(2);
+        Dev<double> dstats(5), dpart((size_t)mg_cfg_stats_partials_bytes() / sizeof(double));
+        const float g = 5.f, phi = 0.7f;
+        int rc = mg_cfg_stats_f32(du.p, dc.p, n, dstats.p, dpart.p, 0);
+        if (!rc) rc = mg_cfg_coef_f32(dstats.p, n, g, 1, phi, dcoef.p, 0);
+        if (!rc) rc = mg_cfg_combine_coef_f32(dout.p, du.p, dc.p, n, dcoef.p, 0);
+        CK(hipDeviceSynchronize());
+        double S[5] = {0, 0, 0, 0, 0};
+        for (int64_t i = 0; i < n; ++i) {
+            const double a = u[i], b = c[i];
+            S[0] += a; S[1] += b; S[2] += a * a; S[3] += b * b; S[4] += a * b;
+        }
+        double au = S[4] / (S[2] + 1e-8) * (1.0 - g), ac = g;
+        const double mp = (au * S[0] + ac * S[1]) / n, ep = (au * au * S[2] + 2.0 * au * ac * S[4] + ac * ac * S[3]) / n, mc = S[1] / n;
+        const double f = phi * sqrt((S[3] / n - mc * mc) / (ep - mp * mp)) + (1.0 - phi);
+        au *= f; ac *= f;
+        auto o = dout.host();
+        double err = rc ? 1e9 : 0;
+        for (int64_t i = 0; i < n; ++i) err = fmax(err, fabs(o[i] - (au * u[i] + ac * c[i])));
+        report("cfg_stats/coef/combine_coef_f32", err, 2e-5);
+    }
 }
 
 static void bench_elementwise(int64_t L, int dim) {

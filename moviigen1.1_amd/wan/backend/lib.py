@@ -51,6 +51,10 @@ SIGNATURES = {
     'mg_unpatchify_f32': [c_vp, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp],
     'mg_lincomb4_f32': [c_vp, c_i64, c_vp, c_f32, c_vp, c_f32, c_vp, c_f32, c_vp, c_f32, c_vp],
     'mg_cfg_combine_f32': [c_vp, c_vp, c_vp, c_f32, c_i64, c_vp],
+    'mg_cfg_stats_partials_bytes': [],
+    'mg_cfg_stats_f32': [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
+    'mg_cfg_coef_f32': [c_vp, c_i64, c_f32, c_int, c_f32, c_vp, c_vp],
+    'mg_cfg_combine_coef_f32': [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp],
     'mg_embed_rows_bf16': [c_vp, c_i64, c_int, c_vp, c_int, c_vp, c_vp],
     'mg_ew_bf16': [c_vp, c_vp, c_vp, c_i64, c_int, c_vp],
     'mg_t5_attn_bf16': [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_vp],
@@ -104,7 +108,7 @@ SIGNATURES_AB = {
     'mg_gemm5_debug_profile': [c_vp],
 }
 _RESTYPE = {'mg_version': ctypes.c_char_p, 'mg_vae_attn_workspace_floats': ctypes.c_int64, 'mg_attn_workspace_bytes': ctypes.c_int64,
-            'mg_step_resid_partials_bytes': ctypes.c_int64, 'mg_attn_w64_profile': None,
+            'mg_step_resid_partials_bytes': ctypes.c_int64, 'mg_cfg_stats_partials_bytes': ctypes.c_int64, 'mg_attn_w64_profile': None,
             'mg_attn_w64_debug': None, 'mg_attn_w64_flag_counter': None, 'mg_gemm_debug_profile': None, 'mg_gemm5_debug_profile': None}
 DEFAULT_GEMM_VARIANT = 0   # mg_gemm_set_variant(0) = the product's rule by shape (A/B library)
 

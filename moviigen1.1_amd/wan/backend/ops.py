@@ -388,6 +388,58 @@ def cfg_combine(out, uncond, cond, g):
     return out
 
 
+def cfg_stats_partials(device):
+    """the caller-owned scratch of cfg_stats: mg_cfg_stats_partials_bytes() bytes as fp64, no initial value needed"""
+    return torch.empty(int(lib.load().mg_cfg_stats_partials_bytes()) // 8, dtype=torch.float64, device=device)
+
+
+def _chk_aligned16(t, name):
+    if t.data_ptr() % 16:
+        raise lib.MoviigenHipError(f'{name}: must be 16-byte aligned (a view that starts inside a row is not)')
+
+
+def cfg_stats(uncond, cond, stats, partials):
+    """stats fp64 [5] <- (sum u, sum c, sum u^2, sum c^2, sum u c) over the dense fp32 tensors uncond (u) and cond (c) of one size:
+    fp64 products and sums in a fixed order (the same inputs give the same 40 bytes), no host read; partials: cfg_stats_partials(device).
+    The inputs are only read.  DESIGN.md 3.8."""
+    _chk_flat(uncond, torch.float32, 'uncond'); _chk_flat(cond, torch.float32, 'cond')
+    _chk_flat(stats, torch.float64, 'stats'); _chk_flat(partials, torch.float64, 'partials')
+    if uncond.numel() < 1 or cond.numel() != uncond.numel():
+        raise lib.MoviigenHipError(f'cfg_stats size mismatch uncond{tuple(uncond.shape)} cond{tuple(cond.shape)} (at least one element)')
+    if stats.numel() != 5 or partials.numel() * 8 < int(lib.load().mg_cfg_stats_partials_bytes()):
+        raise lib.MoviigenHipError('cfg_stats: stats must be fp64 [5] and partials cfg_stats_partials(device)')
+    _chk_aligned16(uncond, 'uncond'); _chk_aligned16(cond, 'cond')
+    lib.call('mg_cfg_stats_f32', _p(uncond), _p(cond), uncond.numel(), _p(stats), _p(partials), _st())
+    return stats
+
+
+def cfg_coefficients(stats, n, g, zero_star, rescale, coef):
+    """coef fp32 [2] <- (a_u, a_c) of the guided prediction a_u u + a_c c from cfg_stats' sums over n elements: guide scale g, CFG-Zero*'s
+    projection when zero_star, guidance rescale by `rescale` in [0, 1] (0 = off) — on the device, in fp64 (include/moviigen_hip.h)."""
+    _chk_flat(stats, torch.float64, 'stats'); _chk_flat(coef, torch.float32, 'coef')
+    g, rescale = float(g), float(rescale)
+    if stats.numel() != 5 or coef.numel() != 2 or int(n) < 1:
+        raise lib.MoviigenHipError(f'cfg_coefficients: stats must be fp64 [5], coef fp32 [2], n >= 1; got {tuple(stats.shape)}, {tuple(coef.shape)}, {n}')
+    if g != g or abs(g) == float('inf') or not 0.0 <= rescale <= 1.0:
+        raise lib.MoviigenHipError(f'cfg_coefficients: g must be finite and rescale in [0, 1], got {g}, {rescale}')
+    lib.call('mg_cfg_coef_f32', _p(stats), int(n), g, int(bool(zero_star)), rescale, _p(coef), _st())
+    return coef
+
+
+def cfg_combine_coef(out, uncond, cond, coef):
+    """out = a_u * uncond + a_c * cond with (a_u, a_c) = coef fp32 [2] ON THE DEVICE (cfg_coefficients): the bits of
+    lincomb(out, [(uncond, a_u), (cond, a_c)]).  Dense fp32 tensors of one size; out may be uncond or cond."""
+    _chk_flat(out, torch.float32, 'out'); _chk_flat(uncond, torch.float32, 'uncond'); _chk_flat(cond, torch.float32, 'cond')
+    _chk_flat(coef, torch.float32, 'coef')
+    if uncond.numel() != out.numel() or cond.numel() != out.numel():
+        raise lib.MoviigenHipError(f'cfg_combine_coef size mismatch out{tuple(out.shape)} uncond{tuple(uncond.shape)} cond{tuple(cond.shape)}')
+    if coef.numel() != 2:
+        raise lib.MoviigenHipError(f'cfg_combine_coef: coef must be fp32 [2], got {tuple(coef.shape)}')
+    _chk_aligned16(out, 'out'); _chk_aligned16(uncond, 'uncond'); _chk_aligned16(cond, 'cond')
+    lib.call('mg_cfg_combine_coef_f32', _p(out), _p(uncond), _p(cond), out.numel(), _p(coef), _st())
+    return out
+
+
 # ---- umT5 encoder glue ---------------------------------------------------------------------------
 def embed_rows(table, ids, out):
     """out [n, dim] = table [vocab, dim][ids [n]] (ids clamped to the table): dense bf16 / int64 tensors, dim a multiple of 8."""

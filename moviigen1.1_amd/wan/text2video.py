@@ -27,6 +27,7 @@ from .modules.model import WanModel
 from .modules.vae import WanVAE
 from .utils.fm_solvers import FlowDPMSolverMultistepScheduler, get_sampling_sigmas, retrieve_timesteps
 from .utils.fm_solvers_unipc import FlowUniPCMultistepScheduler
+from .utils.guidance import Guidance, adjust_step_plan
 from .utils.step_cache import resolve_plan
 
 
@@ -47,11 +48,18 @@ class MaskedEdit:
         self.pm, self.lm, self.clip, self.z0 = pm, lm, None, None
 
 
+def _checked_guidance(guidance):
+    if guidance is not None and not isinstance(guidance, Guidance):
+        raise ValueError(f'guidance must be None or a wan.utils.guidance.Guidance, got {guidance!r}')
+    return guidance
+
+
 class WanT2V:
 
     def __init__(self, config, checkpoint_dir, device_id=0, rank=0, t5_fsdp=False, dit_fsdp=False, use_usp=False,
                  t5_cpu=False, text_encoder=None, model=None, vae=None, cfg_parallel=False, vae_parallel=False, use_ring=False, sp_degrees=None,
-                 dit_gemm='bf16', step_cache=None, lora=None, lora_strength=1.0):
+                 dit_gemm='bf16', step_cache=None, guidance=None, lora=None, lora_strength=1.0):
+        _checked_guidance(guidance)
         self.device = torch.device(f'cuda:{device_id}')
         self.config = config
         self.rank = rank
@@ -121,6 +129,9 @@ class WanT2V:
         # the object's default for generate(step_cache=): None = every step runs the blocks (the reference's loop)
         self.step_cache = step_cache
         self.last_step_plan = self.last_step_timesteps = None
+        # the object's default for generate(guidance=): None = both branches in every step, mixed as u + g (c - u) (the reference's loop)
+        self.guidance = guidance
+        self.last_guidance_plan = None
 
     def _encode(self, prompt):
         if torch.is_tensor(prompt):
@@ -178,6 +189,11 @@ class WanT2V:
         # this half's branch only, then swap predictions with the partner rank
         mine = self.model([latent], t=t, context=context_null if self.cfgp.branch else context, seq_len=seq_len)[0]
         return self.cfgp.exchange(mine)
+
+    def _cond_prediction(self, latent, t, context, seq_len):
+        """the conditional branch alone, of a step outside the guidance interval: ONE forward — the call whose bits forward_pair promises for
+        its cond half.  Under cfg_parallel both halves of the ranks run it (each its own Ulysses group) and nothing is exchanged."""
+        return self.model([latent], t=t, context=context, seq_len=seq_len)[0]
 
     def _scheduler(self, sample_solver, sampling_steps, shift):
         """-> (scheduler, timesteps on the device) of the reference's two solvers (text2video.py:186-207)"""
@@ -246,7 +262,7 @@ class WanT2V:
 
     def generate(self, input_prompt, size=(1280, 720), frame_num=81, shift=5.0, sample_solver='unipc',
                  sampling_steps=50, guide_scale=5.0, n_prompt="", seed=-1, offload_model=True,
-                 noise=None, callback=None, step_cache=None, init_video=None, strength=1.0):
+                 noise=None, callback=None, step_cache=None, guidance=None, init_video=None, strength=1.0):
         """The reference's `generate` (text2video.py:114-271), plus a video-to-video start and a step cache that are NOT part of the reference:
 
         init_video: an existing clip to start from instead of pure noise — uint8 RGB frames [T, H0, W0, 3] of any size (tensor or array;
@@ -264,9 +280,20 @@ class WanT2V:
             explicit plan: one bool per schedule index, True = compute.  The plan is a function of the timesteps and the weights only:
             known before the loop, the same on every rank and for both guidance branches.  The first step that runs is always computed.
             `self.last_step_plan` holds the plan of the last call (None without a step cache); the residuals are dropped when the loop ends.
-            Threshold 0 and an all-True plan give the bits of step_cache=None."""
+            Threshold 0 and an all-True plan give the bits of step_cache=None.
+
+        guidance (default: the object's, WanT2V(guidance=); None = off, the loop above call for call): a wan.utils.guidance.Guidance —
+            which steps run both branches and how the two predictions are mixed.  Its plan, one of 'zero' | 'cond' |
+            'guided' per schedule index, is a function of the schedule alone (`self.last_guidance_plan`; None without a Guidance):
+            'zero' (CFG-Zero*'s zero-init): no forward, the prediction is zero; 'cond' (outside the guidance interval): ONE forward, the
+            conditional branch, and its prediction is used as it is — under cfg_parallel both halves run it and nothing is exchanged;
+            'guided': both branches, mixed as u + g (c - u) by mg_cfg_combine_f32 when neither zero_star nor rescale is on
+            (Guidance(scale=g) alone gives the bits of guide_scale=g), else by the three launches cfg_stats -> cfg_coefficients ->
+            cfg_combine_coef on scratch allocated once per call, every rank on its whole latent (no collective, no host read).
+            With a step cache the residuals are per context, so a 'guided' step is computed when the last step that ran a forward was not
+            'guided', and the first step that runs a forward is computed; `last_step_plan` holds the plan so adjusted."""
         return self._sample(input_prompt, size, frame_num, shift, sample_solver, sampling_steps, guide_scale, n_prompt, seed, offload_model,
-                            noise, callback, step_cache, init_video, strength, edit=None)
+                            noise, callback, step_cache, guidance, init_video, strength, edit=None)
 
     def masked_edit(self, init_video, mask, keep_frames, size, frame_num):
         """`inpaint`'s mask / keep_frames -> MaskedEdit(pm, lm): the mask through the cover / crop geometry of the frames (ops.mask_from_u8), the
@@ -298,7 +325,8 @@ class WanT2V:
 
     def inpaint(self, input_prompt, init_video, mask=None, keep_frames=0, strength=1.0, **kw):
         """Masked video-to-video (NOT part of the reference): keep part of `init_video` and regenerate the rest.  `kw` are `generate`'s other
-        arguments (size, frame_num, shift, sample_solver, sampling_steps, guide_scale, n_prompt, seed, offload_model, noise, callback, step_cache).
+        arguments (size, frame_num, shift, sample_solver, sampling_steps, guide_scale, n_prompt, seed, offload_model, noise, callback, step_cache,
+        guidance).
 
         mask: uint8 or bool, tensor or array, [Tm, H0, W0] (Tm == 1: one mask for every frame, or Tm >= frame_num: the first frame_num are used)
             or [H0, W0], with the spatial size of init_video (the frame size of uint8 frames, `size` for a float clip); >= 128 / True =
@@ -320,8 +348,9 @@ class WanT2V:
         return self._sample(edit=edit, **args.arguments)
 
     def _sample(self, input_prompt, size, frame_num, shift, sample_solver, sampling_steps, guide_scale, n_prompt, seed, offload_model,
-                noise, callback, step_cache, init_video, strength, edit):
+                noise, callback, step_cache, guidance, init_video, strength, edit):
         """the body of `generate` and `inpaint`; edit: None, or inpaint's MaskedEdit"""
+        guidance = _checked_guidance(self.guidance if guidance is None else guidance)
         n_run, i0 = v2v_steps(sampling_steps, strength)
         if init_video is None and i0:
             raise ValueError('strength < 1 needs init_video: there is nothing to start from')
@@ -352,25 +381,49 @@ class WanT2V:
                 keep = {} if edit is None else {'keep': edit}        # (`generate` calls the five-argument form: a replaced start_latent keeps serving it)
                 latent = self.start_latent(init_video, size, frame_num, noise, sample_scheduler.sigmas[i0].item() if i0 else 1.0, **keep)
             timesteps_host = timesteps.tolist()          # ONE sync for the whole loop
-            sigmas_host = sample_scheduler.sigmas.tolist() if edit is not None else None        # (steps + 1 entries, the last one 0)
+            sigmas_host = sample_scheduler.sigmas.tolist() if edit is not None or guidance is not None else None   # (steps + 1 entries, the last one 0)
             if next(self.model.parameters()).device != self.device:     # only after a real offload (a no-op move would
                 self.model.to(self.device)                               # still drop the fused-weight views: 28 GB re-packed)
             noise_pred = torch.empty_like(latent)
             plan, plan_stats = resolve_plan(self.step_cache if step_cache is None else step_cache, self.model, timesteps, i0)
+            kinds = mix = None          # the guidance plan, one of 'zero' | 'cond' | 'guided' per schedule index; None: every step 'guided'
+            if guidance is not None:
+                kinds = guidance.plan(sigmas_host[:len(timesteps_host)], i0)
+                if guidance.scale is not None:
+                    guide_scale = guidance.scale
+                if plan is not None:    # residuals are per context (a rank's own branch only under cfg_parallel): wan/utils/guidance.py
+                    plan = adjust_step_plan(plan, kinds, i0, own_branch_only=self.cfgp is not None)
+                if not guidance.plain_mix and 'guided' in kinds[i0:]:      # the scratch of the three-launch mix, once per call
+                    mix = (torch.empty(5, dtype=torch.float64, device=self.device), ops.cfg_stats_partials(self.device),
+                           torch.empty(2, dtype=torch.float32, device=self.device))
+            self.last_guidance_plan = kinds
             self.last_step_plan = plan
             self.last_step_timesteps = timesteps if plan is not None else None     # what the plan was made of (tools/step_cache_calibrate.py)
             for i, t_host in enumerate(timesteps_host[i0:], start=i0):
                 t = timesteps[i:i + 1]
+                kind = 'guided' if kinds is None else kinds[i]
                 step_mode = contextlib.nullcontext()
                 if plan is not None and not plan[i]:
                     step_mode = self.model.step_cache('skip')
                 elif plan is not None and (plan_stats or (i + 1 < len(plan) and not plan[i + 1])):
                     # a computed step keeps its residual only when the next step adds it again (or the calibration tool asked for the sums)
                     step_mode = self.model.step_cache('compute', stats=plan_stats)
-                with step_mode:
-                    cond, uncond = self._guidance_pair(latent, t, context, context_null, seq_len)
-                ops.cfg_combine(noise_pred, uncond, cond, guide_scale)
-                latent = sample_scheduler.step(noise_pred.unsqueeze(0), t_host, latent.unsqueeze(0),
+                pred = noise_pred
+                if kind == 'zero':          # CFG-Zero*'s zero-init: no forward, the scheduler steps on a zero prediction
+                    noise_pred.zero_()
+                elif kind == 'cond':        # outside the guidance interval: the conditional branch alone, its prediction as it is (a new
+                    with step_mode:         # tensor of every forward)
+                        pred = self._cond_prediction(latent, t, context, seq_len)
+                else:
+                    with step_mode:
+                        cond, uncond = self._guidance_pair(latent, t, context, context_null, seq_len)
+                    if mix is None:
+                        ops.cfg_combine(noise_pred, uncond, cond, guide_scale)
+                    else:                   # CFG-Zero* / rescale: five fp64 sums, two coefficients, the mix: no host read
+                        ops.cfg_stats(uncond, cond, mix[0], mix[1])
+                        ops.cfg_coefficients(mix[0], noise_pred.numel(), guide_scale, guidance.zero_star, guidance.rescale, mix[2])
+                        ops.cfg_combine_coef(noise_pred, uncond, cond, mix[2])
+                latent = sample_scheduler.step(pred.unsqueeze(0), t_host, latent.unsqueeze(0),
                                                return_dict=False, generator=seed_g)[0].squeeze(0)
                 if edit is not None:        # the step left the latent at sigma_{i+1}: put the kept cells back at that noise level
                     ops.masked_renoise(latent, edit.z0, noise, edit.lm, 1.0 - sigmas_host[i + 1], sigmas_host[i + 1])

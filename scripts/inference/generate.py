@@ -18,7 +18,10 @@ the first N frames, regenerate the rest),
 `--step_cache THRESH` / `--step_cache_coefficients a,b,c,d,e` / `--step_cache_keep FIRST,LAST` (opt-in step cache,
 `WanT2V.generate(step_cache=)`: steps whose time embedding has barely moved skip the DiT blocks and add the last computed step's
 residual again; the coefficients come from `tools/step_cache_calibrate.py` on the real checkpoint — no threshold is recommended
-without that calibration) and
+without that calibration),
+`--guide_interval LO,HI` / `--cfg_zero_star` / `--cfg_zero_init N` / `--guide_rescale PHI` (opt-in guidance options,
+`WanT2V.generate(guidance=)`, DESIGN.md §3.8: both branches only while sigma lies in [LO, HI], CFG-Zero*'s projection and zero-init,
+guidance rescale; no values are recommended) and
 `--prompt_embeds FILE` (a torch file {'prompt': [len,4096], 'negative': [len,4096]} instead of running
 umT5 — for boxes without the tokenizer files)."""
 import argparse
@@ -96,6 +99,16 @@ FLAGS = [
                                             'predicted output change, as tools/step_cache_calibrate.py prints it; default 0,0,0,1,0 (the raw distance).')),
     ('--step_cache_keep', dict(type=str, default=None, metavar='FIRST,LAST',
                                help='with --step_cache: always compute the first FIRST and the last LAST steps (default 1,1).')),
+    ('--guide_interval', dict(type=str, default=None, metavar='LO,HI',
+                              help='opt-in guidance interval: both guidance branches run only while the noise level sigma of a step lies in [LO, HI] '
+                                   '(0 <= LO <= HI <= 1); outside it only the conditional branch runs, one DiT forward instead of two. Not the reference '
+                                   'arithmetic; off by default.')),
+    ('--cfg_zero_star', dict(action='store_true', default=False,
+                             help='opt-in CFG-Zero*: the unconditional prediction is rescaled by its projection <c,u>/|u|^2 before the guidance mix.')),
+    ('--cfg_zero_init', dict(type=int, default=0, metavar='N', help='opt-in CFG-Zero* zero-init: the first N steps predict zero and run no DiT forward.')),
+    ('--guide_rescale', dict(type=float, default=0.0, metavar='PHI',
+                             help='opt-in guidance rescale: the guided prediction is pulled towards the standard deviation of the conditional one by '
+                                  'PHI in [0, 1] (0 = off).')),
     ('--prompt_embeds', dict(type=str, default=None, help="torch file {'prompt','negative'} of umT5 embeddings, replaces the text encoder.")),
 ]
 
@@ -138,6 +151,24 @@ def _step_cache_spec(args):
     return spec
 
 
+def _guidance_spec(args):
+    """the four guidance flags -> WanT2V.generate's `guidance` argument (None when none of them is given)"""
+    if args.guide_interval is None and not args.cfg_zero_star and args.cfg_zero_init == 0 and args.guide_rescale == 0.0:
+        return None
+    from wan.utils.guidance import Guidance
+    interval = (0.0, 1.0)
+    if args.guide_interval is not None:
+        try:
+            interval = tuple(float(v) for v in args.guide_interval.split(','))
+        except ValueError:
+            interval = ()
+        assert len(interval) == 2, f'--guide_interval must be LO,HI (two numbers), got {args.guide_interval!r}'
+    try:
+        return Guidance(interval=interval, zero_star=args.cfg_zero_star, zero_init_steps=args.cfg_zero_init, rescale=args.guide_rescale)
+    except ValueError as e:
+        raise AssertionError(f'--guide_interval / --cfg_zero_init / --guide_rescale: {e}') from None
+
+
 def _validate_args(args):
     assert args.ckpt_dir is not None, 'Please specify the checkpoint directory.'
     assert args.task in WAN_CONFIGS, f'Unsupport task: {args.task}'
@@ -158,6 +189,7 @@ def _validate_args(args):
     assert 0 <= args.keep_frames <= args.frame_num, f'--keep_frames must be in [0, {args.frame_num}], got {args.keep_frames}'
     args.lora = [_lora_arg(a) for a in args.lora or []]
     args.step_cache_spec = _step_cache_spec(args)
+    args.guidance = _guidance_spec(args)
     assert args.size in SUPPORTED_SIZES[args.task], \
         f"Unsupport size {args.size} for task {args.task}, supported sizes are: {', '.join(SUPPORTED_SIZES[args.task])}"
 
@@ -239,6 +271,9 @@ def generate(args):
     if args.init_video:         # every rank reads the file and encodes the clip for itself
         v2v = dict(init_video=load_video(args.init_video), strength=args.strength)
         logging.info(f"video-to-video start from {args.init_video}: {v2v['init_video'].shape[0]} frames, strength {args.strength}")
+    if args.guidance is not None:       # (without a guidance flag the call is the one it was)
+        v2v['guidance'] = args.guidance
+        logging.info(f'guidance options: {args.guidance}')
     run = pipe.generate
     if args.mask or args.keep_frames:       # masked video-to-video: the same call through WanT2V.inpaint
         v2v.update(mask=load_mask(args.mask) if args.mask else None, keep_frames=args.keep_frames)
@@ -251,6 +286,9 @@ def generate(args):
     if pipe.last_step_plan is not None:
         logging.info('step cache: computed %d of %d steps: %s' % (sum(pipe.last_step_plan), len(pipe.last_step_plan),
                                                                    ''.join('C' if c else 's' for c in pipe.last_step_plan)))
+    if getattr(pipe, 'last_guidance_plan', None) is not None:
+        logging.info('guidance plan (z = zero, c = conditional branch only, G = both branches): ' + ''.join(
+            {'zero': 'z', 'cond': 'c', 'guided': 'G'}[k] for k in pipe.last_guidance_plan))
     if rank == 0:
         if args.save_file is None:
             args.save_file = default_save_name(args)

@@ -9,6 +9,8 @@ output contract (ids, mask of text_len 512); everything behind it is the product
 usage: python tools/e2e_video.py [--workload 1080p|720p] [--steps 50] [--solver unipc] [--step_cache SPEC]      -> one JSON line on stdout
 --step_cache (opt-in step cache): a threshold (a number), or an explicit plan of C (compute) / S (skip) letters, repeated to
 --steps entries — `CS` = every other step.
+--guide_interval LO,HI / --cfg_zero_star / --cfg_zero_init N / --guide_rescale PHI (opt-in guidance options): the launcher's flags; the
+line then carries the median wall time of the 'guided', 'cond' and 'zero' steps separately.
 """
 import argparse
 import json
@@ -49,7 +51,17 @@ def main():
     ap.add_argument('--prompt-words', type=int, default=511)
     ap.add_argument('--neg-words', type=int, default=129)
     ap.add_argument('--step_cache', default=None, help='threshold, or a plan of C / S letters repeated over the steps (CS = every other step)')
+    # the launcher's guidance flags (scripts/inference/generate.py)
+    ap.add_argument('--guide_interval', default=None, metavar='LO,HI', help='both guidance branches only while sigma lies in [LO, HI]')
+    ap.add_argument('--cfg_zero_star', action='store_true', help="CFG-Zero*'s projection in the guided steps")
+    ap.add_argument('--cfg_zero_init', type=int, default=0, metavar='N', help='the first N steps predict zero')
+    ap.add_argument('--guide_rescale', type=float, default=0.0, metavar='PHI', help='guidance rescale in [0, 1]')
     args = ap.parse_args()
+    guidance = None
+    if args.guide_interval is not None or args.cfg_zero_star or args.cfg_zero_init or args.guide_rescale:
+        from wan.utils.guidance import Guidance
+        interval = tuple(float(v) for v in args.guide_interval.split(',')) if args.guide_interval is not None else (0.0, 1.0)
+        guidance = Guidance(interval=interval, zero_star=args.cfg_zero_star, zero_init_steps=args.cfg_zero_init, rescale=args.guide_rescale)
     step_cache = None
     if args.step_cache is not None:
         pat = args.step_cache.upper()
@@ -97,7 +109,7 @@ def main():
     t0 = time.perf_counter()
     start.record()
     video = pipe.generate(prompt, size=size, frame_num=81, sampling_steps=args.steps, sample_solver=args.solver, n_prompt=negative, seed=42,
-                          offload_model=True, callback=callback, step_cache=step_cache)
+                          offload_model=True, callback=callback, step_cache=step_cache, **({} if guidance is None else {'guidance': guidance}))
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     t1 = time.perf_counter()
@@ -113,7 +125,12 @@ def main():
     by_kind = {} if plan is None else {     # a step as the loop sees it: the forward(s) + CFG + the scheduler update (step 0 left out: prompt caches)
         'median_computed_step_ms': med([m for m, c in list(zip(step_ms, plan))[1:] if c]),
         'median_skipped_step_ms': med([m for m, c in list(zip(step_ms, plan))[1:] if not c])}
-    line = {'what': 'WanT2V.generate end to end (tools/e2e_video.py): text encoder x 2 prompts + %d denoising steps (two guidance branches through WanModel.forward_pair, CFG 5.0, %s) '
+    kinds = pipe.last_guidance_plan
+    if kinds is not None:       # the wall time of a step by what the guidance plan made of it (step 0 left out as above)
+        by_kind.update({f'median_{k}_step_ms': med([m for m, kk in list(zip(step_ms, kinds))[1:] if kk == k]) for k in ('guided', 'cond', 'zero')})
+        by_kind.update({'guidance': repr(guidance), 'guidance_plan': ''.join({'zero': 'z', 'cond': 'c', 'guided': 'G'}[k] for k in kinds),
+                        'step_ms': [round(m, 1) for m in step_ms]})
+    line = {'what':'WanT2V.generate end to end (tools/e2e_video.py): text encoder x 2 prompts + %d denoising steps (two guidance branches through WanModel.forward_pair, CFG 5.0, %s) '
                     '+ WanVAE.decode, offload_model=True (the reference default), one call on the wall clock' % (args.steps, args.solver),
             'workload': '14B T2V %dx%dx81f' % size, 'sampling_steps': args.steps,
             'step_cache': args.step_cache, **by_kind, 'steps_computed': sum(pipe.last_step_plan) if pipe.last_step_plan is not None else args.steps, 'sec_per_video_measured': wall,
