@@ -521,6 +521,27 @@ int mg_masked_renoise_f32(float* latent, const float* z0, const float* noise, co
  * 16-byte accesses when video and src are 16-byte aligned; any hw. */
 int mg_mask_composite_f32(float* video, const float* src, const uint8_t* pm, int T, int64_t hw, void* stream);
 
+/* Context windows (additions to ABI 9; not in the reference): WanT2V.generate(windows=) denoises a latent longer than one DiT
+ * pass as a whole and shows it to the DiT through overlapping windows of Fw latent frames.  The two functions move between the whole clip
+ * [C][F][hw] and one window [C][Fw][hw] at frames [f0, f0 + Fw); all fp32, dense.  They use no device memory of their own and no atomics;
+ * every output element is written by one thread: run-to-run identical, capturable.  A non-positive C, F, hw or Fw, f0 < 0 or
+ * f0 + Fw > F is MG_ERR_SHAPE (checked before the pointers), a null pointer MG_ERR_ARG.  All index arithmetic is 64-bit.  A row of hw
+ * elements goes as 16-byte accesses when both of its addresses are 16-byte aligned — the row (c, f0 + j) of the whole clip starts
+ * (c F + f0 + j) hw elements behind the base, so that depends on F, f0 and hw as well as on the pointers — and element by element
+ * otherwise; any hw, no pointer needs more than its type's alignment.
+ *
+ * mg_window_gather_f32: out[c][j][p] = x[c][f0 + j][p], a copy (the bits are unchanged).  x is only read, out is written once, every element.
+ *
+ * mg_window_blend_f32: with w[Fw] and first[Fw] in DEVICE memory, for every c, j, p, a = acc[c][f0 + j][p] and v = pred[c][j][p]:
+ *   first[j] != 0: acc = w[j] v.  A select: the old content of acc is not read, so it needs no initial value and a NaN in it does not
+ *                  reach the result;
+ *   first[j] == 0: acc = fma(w[j], v, a).
+ * One rounding per element and call; w[j] == 1.0f with first[j] != 0 leaves the bits of v.  Frames of acc outside [f0, f0 + Fw) are not
+ * touched.  pred, w and first are only read; acc and pred must not overlap. */
+int mg_window_gather_f32(const float* x, int C, int64_t F, int64_t hw, int64_t f0, int Fw, float* out, void* stream);
+int mg_window_blend_f32(float* acc, const float* pred, int C, int64_t F, int64_t hw, int64_t f0, int Fw, const float* w, const uint8_t* first,
+                        void* stream);
+
 /* time_conv channel halves -> interleaved frames (vae.py:133-137):
  * x [T][H][W][2C] -> out [2T][H][W][C], frame 2t from channels [0,C), 2t+1 from [C,2C). */
 int mg_vae_time_interleave_f32(const float* x, int T, int64_t HW, int C, float* out, void* stream);

@@ -638,6 +638,35 @@ static void test_small() {
         for (int64_t i = 0; i < n; ++i) err = fmax(err, fabs(o[i] - (au * u[i] + ac * c[i])));
         report("cfg_stats/coef/combine_coef_f32", err, 2e-5);
     }
+    {  // context windows: three windows of 3 frames over 7 (starts 0, 2, 4; pyramid weights), gathered and blended back: hw = 35 makes
+       // rows that are not 16-byte aligned, hw = 36 aligned ones.  Blending the gathered windows with weights that sum to 1 per frame
+       // gives the clip back, up to the roundings of the weights and of one product or fma per window
+        for (const int64_t hw : {35, 36}) {
+            const int C = 3, Fw = 3; const int64_t F = 7, starts[3] = {0, 2, 4};
+            const float wgt[3][3] = {{1.f, 1.f, 0.5f}, {0.5f, 1.f, 0.5f}, {0.5f, 1.f, 1.f}};
+            const uint8_t fst[3][3] = {{1, 1, 1}, {0, 1, 1}, {0, 1, 1}};
+            auto x = randf((size_t)C * F * hw);
+            std::vector<float> nanfill((size_t)C * F * hw, NAN);
+            Dev<float> dx(x), dwin((size_t)C * Fw * hw), dacc(nanfill), dw(3);
+            Dev<uint8_t> df(3);
+            int rc = 0;
+            double err = 0;
+            for (int k = 0; k < 3 && !rc; ++k) {
+                CK(hipMemcpy(dw.p, wgt[k], sizeof(wgt[k]), hipMemcpyHostToDevice));
+                CK(hipMemcpy(df.p, fst[k], sizeof(fst[k]), hipMemcpyHostToDevice));
+                rc = mg_window_gather_f32(dx.p, C, F, hw, starts[k], Fw, dwin.p, 0);
+                if (!rc) rc = mg_window_blend_f32(dacc.p, dwin.p, C, F, hw, starts[k], Fw, dw.p, df.p, 0);
+                CK(hipDeviceSynchronize());
+                auto win = dwin.host();
+                for (int c = 0; c < C; ++c) for (int j = 0; j < Fw; ++j) for (int64_t p = 0; p < hw; ++p)
+                    if (win[((size_t)c * Fw + j) * hw + p] != x[((size_t)c * F + starts[k] + j) * hw + p]) err = 1e9;
+            }
+            auto o = dacc.host();
+            if (rc) err = 1e9;
+            for (size_t i = 0; i < o.size(); ++i) err = fmax(err, o[i] == o[i] ? fabs((double)o[i] - x[i]) : 1e9);
+            report(hw == 35 ? "window_gather/blend_f32 hw35" : "window_gather/blend_f32 hw36", err, 1e-6);
+        }
+    }
 }
 
 static void bench_elementwise(int64_t L, int dim) {

@@ -83,6 +83,8 @@ SIGNATURES = {
     'mg_mask_to_latent_u8': [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp],
     'mg_masked_renoise_f32': [c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_int, c_i64, c_vp],
     'mg_mask_composite_f32': [c_vp, c_vp, c_vp, c_int, c_i64, c_vp],
+    'mg_window_gather_f32': [c_vp, c_int, c_i64, c_i64, c_i64, c_int, c_vp, c_vp],
+    'mg_window_blend_f32': [c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp],
     'mg_lora_merge': [c_vp, c_int, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_int, c_vp],
     'mg_comm_unique_id': [c_vp],
     'mg_comm_create': [c_vp, c_int, c_int, c_vp],

@@ -824,6 +824,36 @@ def mask_composite(video, src, pm):
     return video
 
 
+def _window_dims(name, whole, win, f0):
+    """(C, F, hw, Fw) of a whole clip [C, F, ...] and one window [C, Fw, ...] of it at frames [f0, f0 + Fw), both dense fp32"""
+    _chk_flat(whole, torch.float32, name[0]); _chk_flat(win, torch.float32, name[1])
+    if whole.dim() < 2 or win.dim() != whole.dim() or win.shape[0] != whole.shape[0] or tuple(win.shape[2:]) != tuple(whole.shape[2:]) \
+            or min(whole.shape) < 1 or win.shape[1] < 1 or not 0 <= int(f0) <= whole.shape[1] - win.shape[1]:
+        raise lib.MoviigenHipError(f'{name[0]} {tuple(whole.shape)} and {name[1]} {tuple(win.shape)} must be [C, F, ...] and [C, Fw, ...] with '
+                                   f'0 <= f0 <= F - Fw, f0 = {f0}')
+    C, F, Fw = whole.shape[0], whole.shape[1], win.shape[1]
+    return C, F, whole.numel() // (C * F), Fw
+
+
+def window_gather(x, f0, out):
+    """out [C, Fw, ...] <- x[:, f0:f0 + Fw] of the dense fp32 clip x [C, F, ...]: a copy, the bits are unchanged (mg_window_gather_f32)."""
+    C, F, hw, Fw = _window_dims(('x', 'out'), x, out, f0)
+    lib.call('mg_window_gather_f32', _p(x), C, F, hw, int(f0), Fw, _p(out), _st())
+    return out
+
+
+def window_blend(acc, pred, f0, w, first):
+    """acc [C, F, ...] fp32 IN PLACE at frames [f0, f0 + Fw), from the window's prediction pred [C, Fw, ...]: w[j] * pred where first[j]
+    is non-zero (a select: acc is not read there and needs no initial value), fma(w[j], pred, acc) where it is zero.  w fp32 [Fw] and
+    first uint8 [Fw] live on the device; frames outside the window are not touched (mg_window_blend_f32)."""
+    C, F, hw, Fw = _window_dims(('acc', 'pred'), acc, pred, f0)
+    _chk_flat(w, torch.float32, 'w'); _chk_flat(first, torch.uint8, 'first')
+    if tuple(w.shape) != (Fw,) or tuple(first.shape) != (Fw,):
+        raise lib.MoviigenHipError(f'window_blend: w and first must be [{Fw}], got {tuple(w.shape)}, {tuple(first.shape)}')
+    lib.call('mg_window_blend_f32', _p(acc), _p(pred), C, F, hw, int(f0), Fw, _p(w), _p(first), _st())
+    return acc
+
+
 def gate_residual(x, y, gate=None):
     """x [rows, dim] fp32 += y [rows, dim] bf16 * gate [dim] fp32 (None = 1)."""
     _chk(x, torch.float32, 'x'); _chk(y, torch.bfloat16, 'y'); _chk(gate, torch.float32, 'gate')

@@ -27,6 +27,7 @@ from .modules.model import WanModel
 from .modules.vae import WanVAE
 from .utils.fm_solvers import FlowDPMSolverMultistepScheduler, get_sampling_sigmas, retrieve_timesteps
 from .utils.fm_solvers_unipc import FlowUniPCMultistepScheduler
+from .utils.context_windows import ContextWindows
 from .utils.guidance import Guidance, adjust_step_plan
 from .utils.step_cache import resolve_plan
 
@@ -54,12 +55,34 @@ def _checked_guidance(guidance):
     return guidance
 
 
+def _checked_windows(windows):
+    if windows is not None and not isinstance(windows, ContextWindows):
+        raise ValueError(f'windows must be None or a wan.utils.context_windows.ContextWindows, got {windows!r}')
+    return windows
+
+
+class WindowRun:
+    """what a `generate` call with context windows allocates once and every step reuses: the plan (a WindowPlan), the gather buffer `lat`
+    [C, Fw, h, w], the whole-clip predictions `cond` and `uncond` [C, F, h, w] (uncond: None when no step of the call runs both branches),
+    the per-window weights `w` [K, Fw] fp32 and first-cover flags `first` [K, Fw] uint8 on the device, and the DiT's seq_len of ONE window."""
+
+    def __init__(self, plan, latent, both, patch_size, sp_size):
+        C, _, h, w = latent.shape
+        self.plan = plan
+        self.lat = latent.new_empty(C, plan.Fw, h, w)
+        self.cond = torch.empty_like(latent)
+        self.uncond = torch.empty_like(latent) if both else None
+        self.w, self.first = plan.weights.to(latent.device), plan.first.to(latent.device)
+        self.seq_len = math.ceil((h * w) / (patch_size[1] * patch_size[2]) * plan.Fw / sp_size) * sp_size
+
+
 class WanT2V:
 
     def __init__(self, config, checkpoint_dir, device_id=0, rank=0, t5_fsdp=False, dit_fsdp=False, use_usp=False,
                  t5_cpu=False, text_encoder=None, model=None, vae=None, cfg_parallel=False, vae_parallel=False, use_ring=False, sp_degrees=None,
-                 dit_gemm='bf16', step_cache=None, guidance=None, lora=None, lora_strength=1.0):
+                 dit_gemm='bf16', step_cache=None, guidance=None, windows=None, lora=None, lora_strength=1.0):
         _checked_guidance(guidance)
+        _checked_windows(windows)
         self.device = torch.device(f'cuda:{device_id}')
         self.config = config
         self.rank = rank
@@ -132,6 +155,9 @@ class WanT2V:
         # the object's default for generate(guidance=): None = both branches in every step, mixed as u + g (c - u) (the reference's loop)
         self.guidance = guidance
         self.last_guidance_plan = None
+        # the object's default for generate(windows=): None = the whole latent in one DiT pass (the reference's loop)
+        self.windows = windows
+        self.last_window_plan = None
 
     def _encode(self, prompt):
         if torch.is_tensor(prompt):
@@ -194,6 +220,20 @@ class WanT2V:
         """the conditional branch alone, of a step outside the guidance interval: ONE forward — the call whose bits forward_pair promises for
         its cond half.  Under cfg_parallel both halves of the ranks run it (each its own Ulysses group) and nothing is exchanged."""
         return self.model([latent], t=t, context=context, seq_len=seq_len)[0]
+
+    def _window_predictions(self, run, latent, t, context, context_null):
+        """the whole-clip (cond, uncond) predictions of one step through context windows (`run`: the call's WindowRun): every window in
+        ascending order is cut out of the latent, predicted on its own at positions 0 .. Fw - 1 and blended into the whole-clip buffers.
+        context_null None: the conditional branch alone (a 'cond' step) -> (cond, None).  No host read."""
+        for k, f0 in enumerate(run.plan.starts):
+            ops.window_gather(latent, f0, run.lat)
+            if context_null is None:
+                cond, uncond = self._cond_prediction(run.lat, t, context, run.seq_len), None
+            else:
+                cond, uncond = self._guidance_pair(run.lat, t, context, context_null, run.seq_len)
+                ops.window_blend(run.uncond, uncond, f0, run.w[k], run.first[k])
+            ops.window_blend(run.cond, cond, f0, run.w[k], run.first[k])
+        return run.cond, None if context_null is None else run.uncond
 
     def _scheduler(self, sample_solver, sampling_steps, shift):
         """-> (scheduler, timesteps on the device) of the reference's two solvers (text2video.py:186-207)"""
@@ -262,7 +302,7 @@ class WanT2V:
 
     def generate(self, input_prompt, size=(1280, 720), frame_num=81, shift=5.0, sample_solver='unipc',
                  sampling_steps=50, guide_scale=5.0, n_prompt="", seed=-1, offload_model=True,
-                 noise=None, callback=None, step_cache=None, guidance=None, init_video=None, strength=1.0):
+                 noise=None, callback=None, step_cache=None, guidance=None, windows=None, init_video=None, strength=1.0):
         """The reference's `generate` (text2video.py:114-271), plus a video-to-video start and a step cache that are NOT part of the reference:
 
         init_video: an existing clip to start from instead of pure noise — uint8 RGB frames [T, H0, W0, 3] of any size (tensor or array;
@@ -291,9 +331,20 @@ class WanT2V:
             (Guidance(scale=g) alone gives the bits of guide_scale=g), else by the three launches cfg_stats -> cfg_coefficients ->
             cfg_combine_coef on scratch allocated once per call, every rank on its whole latent (no collective, no host read).
             With a step cache the residuals are per context, so a 'guided' step is computed when the last step that ran a forward was not
-            'guided', and the first step that runs a forward is computed; `last_step_plan` holds the plan so adjusted."""
+            'guided', and the first step that runs a forward is computed; `last_step_plan` holds the plan so adjusted.
+
+        windows (default: the object's, WanT2V(windows=); None = off, the loop above call for call): a wan.utils.context_windows.ContextWindows
+            — a clip longer than one DiT pass.  The latent is denoised as a whole; in every step each window of Fw latent
+            frames (ascending starts, `self.last_window_plan`; None without windows or when the clip fits one window, which is the loop
+            above call for call) is cut out (ops.window_gather), predicted on its own at positions 0 .. Fw - 1 with the window's seq_len,
+            and blended with its per-frame weights into whole-clip cond / uncond buffers (ops.window_blend); the guidance mix above then runs
+            ONCE on the whole-clip buffers, so the statistics of CFG-Zero* / rescale are over the whole clip.  A 'cond' step runs one
+            forward per window, a 'zero' step none.  Scheduler step, masked_renoise, `callback(i, whole latent)`, decode and composite are
+            unchanged: init_video, strength and `inpaint` work at any length.  The buffers and the device copies of the weights are
+            allocated once per call; no host read in the loop.  Not together with a step cache (its residuals would be per window):
+            ValueError before any forward."""
         return self._sample(input_prompt, size, frame_num, shift, sample_solver, sampling_steps, guide_scale, n_prompt, seed, offload_model,
-                            noise, callback, step_cache, guidance, init_video, strength, edit=None)
+                            noise, callback, step_cache, guidance, windows, init_video, strength, edit=None)
 
     def masked_edit(self, init_video, mask, keep_frames, size, frame_num):
         """`inpaint`'s mask / keep_frames -> MaskedEdit(pm, lm): the mask through the cover / crop geometry of the frames (ops.mask_from_u8), the
@@ -326,7 +377,7 @@ class WanT2V:
     def inpaint(self, input_prompt, init_video, mask=None, keep_frames=0, strength=1.0, **kw):
         """Masked video-to-video (NOT part of the reference): keep part of `init_video` and regenerate the rest.  `kw` are `generate`'s other
         arguments (size, frame_num, shift, sample_solver, sampling_steps, guide_scale, n_prompt, seed, offload_model, noise, callback, step_cache,
-        guidance).
+        guidance, windows).
 
         mask: uint8 or bool, tensor or array, [Tm, H0, W0] (Tm == 1: one mask for every frame, or Tm >= frame_num: the first frame_num are used)
             or [H0, W0], with the spatial size of init_video (the frame size of uint8 frames, `size` for a float clip); >= 128 / True =
@@ -348,9 +399,10 @@ class WanT2V:
         return self._sample(edit=edit, **args.arguments)
 
     def _sample(self, input_prompt, size, frame_num, shift, sample_solver, sampling_steps, guide_scale, n_prompt, seed, offload_model,
-                noise, callback, step_cache, guidance, init_video, strength, edit):
+                noise, callback, step_cache, guidance, windows, init_video, strength, edit):
         """the body of `generate` and `inpaint`; edit: None, or inpaint's MaskedEdit"""
         guidance = _checked_guidance(self.guidance if guidance is None else guidance)
+        windows = _checked_windows(self.windows if windows is None else windows)
         n_run, i0 = v2v_steps(sampling_steps, strength)
         if init_video is None and i0:
             raise ValueError('strength < 1 needs init_video: there is nothing to start from')
@@ -359,6 +411,13 @@ class WanT2V:
                         size[0] // self.vae_stride[2])
         seq_len = math.ceil((target_shape[2] * target_shape[3]) / (self.patch_size[1] * self.patch_size[2]) *
                             target_shape[1] / self.sp_size) * self.sp_size
+        wplan = None                # the context windows of this call: a function of the latent's length alone; None = one pass, the loop as it was
+        if windows is not None:
+            if windows.stride != self.vae_stride[0]:
+                raise ValueError(f'windows: {windows!r} counts frames for a temporal VAE stride of {windows.stride}, this pipeline has {self.vae_stride[0]}')
+            wplan = windows.plan(target_shape[1])
+        if wplan is not None and (self.step_cache if step_cache is None else step_cache) is not None:
+            raise ValueError('windows cannot be combined with step_cache: the cached residuals would be per window (not built); pass step_cache=None')
         if isinstance(n_prompt, str) and n_prompt == "":
             n_prompt = self.sample_neg_prompt
         seed = seed if seed >= 0 else random.randint(0, sys.maxsize)
@@ -397,6 +456,10 @@ class WanT2V:
                     mix = (torch.empty(5, dtype=torch.float64, device=self.device), ops.cfg_stats_partials(self.device),
                            torch.empty(2, dtype=torch.float32, device=self.device))
             self.last_guidance_plan = kinds
+            self.last_window_plan = None if wplan is None else list(wplan.starts)
+            wrun = None                 # buffers and device arrays of the windowed steps, once per call
+            if wplan is not None:
+                wrun = WindowRun(wplan, latent, kinds is None or 'guided' in kinds[i0:], self.patch_size, self.sp_size)
             self.last_step_plan = plan
             self.last_step_timesteps = timesteps if plan is not None else None     # what the plan was made of (tools/step_cache_calibrate.py)
             for i, t_host in enumerate(timesteps_host[i0:], start=i0):
@@ -413,10 +476,12 @@ class WanT2V:
                     noise_pred.zero_()
                 elif kind == 'cond':        # outside the guidance interval: the conditional branch alone, its prediction as it is (a new
                     with step_mode:         # tensor of every forward)
-                        pred = self._cond_prediction(latent, t, context, seq_len)
+                        pred = (self._cond_prediction(latent, t, context, seq_len) if wrun is None else
+                                self._window_predictions(wrun, latent, t, context, None)[0])
                 else:
                     with step_mode:
-                        cond, uncond = self._guidance_pair(latent, t, context, context_null, seq_len)
+                        cond, uncond = (self._guidance_pair(latent, t, context, context_null, seq_len) if wrun is None else
+                                        self._window_predictions(wrun, latent, t, context, context_null))
                     if mix is None:
                         ops.cfg_combine(noise_pred, uncond, cond, guide_scale)
                     else:                   # CFG-Zero* / rescale: five fp64 sums, two coefficients, the mix: no host read

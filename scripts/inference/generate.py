@@ -21,7 +21,10 @@ residual again; the coefficients come from `tools/step_cache_calibrate.py` on th
 without that calibration),
 `--guide_interval LO,HI` / `--cfg_zero_star` / `--cfg_zero_init N` / `--guide_rescale PHI` (opt-in guidance options,
 `WanT2V.generate(guidance=)`, DESIGN.md §3.8: both branches only while sigma lies in [LO, HI], CFG-Zero*'s projection and zero-init,
-guidance rescale; no values are recommended) and
+guidance rescale; no values are recommended),
+`--context_frames N` / `--context_overlap M` / `--context_fuse pyramid|flat` (opt-in context windows, `WanT2V.generate(windows=)`,
+DESIGN.md §3.9: a `--frame_num` longer than one DiT pass is denoised as a whole through overlapping windows of N frames; no values are
+recommended) and
 `--prompt_embeds FILE` (a torch file {'prompt': [len,4096], 'negative': [len,4096]} instead of running
 umT5 — for boxes without the tokenizer files)."""
 import argparse
@@ -109,6 +112,13 @@ FLAGS = [
     ('--guide_rescale', dict(type=float, default=0.0, metavar='PHI',
                              help='opt-in guidance rescale: the guided prediction is pulled towards the standard deviation of the conditional one by '
                                   'PHI in [0, 1] (0 = off).')),
+    ('--context_frames', dict(type=int, default=None, metavar='N',
+                              help='opt-in context windows for a --frame_num longer than one DiT pass: the clip is denoised as a whole, the DiT sees '
+                                   'it through overlapping windows of N frames (4n+1). Not the reference loop; off by default.')),
+    ('--context_overlap', dict(type=int, default=16, metavar='M',
+                               help='with --context_frames: the frames two neighbouring windows share (a multiple of 4, below N).')),
+    ('--context_fuse', dict(type=str, default='pyramid', choices=['pyramid', 'flat'],
+                            help='with --context_frames: the weight of a frame inside its window when overlapping predictions are blended.')),
     ('--prompt_embeds', dict(type=str, default=None, help="torch file {'prompt','negative'} of umT5 embeddings, replaces the text encoder.")),
 ]
 
@@ -169,6 +179,19 @@ def _guidance_spec(args):
         raise AssertionError(f'--guide_interval / --cfg_zero_init / --guide_rescale: {e}') from None
 
 
+def _windows_spec(args):
+    """the three --context_* flags -> WanT2V.generate's `windows` argument (None without --context_frames)"""
+    if args.context_frames is None:
+        return None
+    from wan.utils.context_windows import ContextWindows
+    try:
+        windows = ContextWindows(frames=args.context_frames, overlap=args.context_overlap, fuse=args.context_fuse)
+    except ValueError as e:
+        raise AssertionError(f'--context_frames / --context_overlap / --context_fuse: {e}') from None
+    assert args.step_cache is None, '--context_frames cannot be combined with --step_cache (the cached residuals would be per window)'
+    return windows
+
+
 def _validate_args(args):
     assert args.ckpt_dir is not None, 'Please specify the checkpoint directory.'
     assert args.task in WAN_CONFIGS, f'Unsupport task: {args.task}'
@@ -190,6 +213,7 @@ def _validate_args(args):
     args.lora = [_lora_arg(a) for a in args.lora or []]
     args.step_cache_spec = _step_cache_spec(args)
     args.guidance = _guidance_spec(args)
+    args.windows = _windows_spec(args)
     assert args.size in SUPPORTED_SIZES[args.task], \
         f"Unsupport size {args.size} for task {args.task}, supported sizes are: {', '.join(SUPPORTED_SIZES[args.task])}"
 
@@ -274,6 +298,9 @@ def generate(args):
     if args.guidance is not None:       # (without a guidance flag the call is the one it was)
         v2v['guidance'] = args.guidance
         logging.info(f'guidance options: {args.guidance}')
+    if args.windows is not None:        # (likewise)
+        v2v['windows'] = args.windows
+        logging.info(f'context windows: {args.windows}')
     run = pipe.generate
     if args.mask or args.keep_frames:       # masked video-to-video: the same call through WanT2V.inpaint
         v2v.update(mask=load_mask(args.mask) if args.mask else None, keep_frames=args.keep_frames)
@@ -289,6 +316,8 @@ def generate(args):
     if getattr(pipe, 'last_guidance_plan', None) is not None:
         logging.info('guidance plan (z = zero, c = conditional branch only, G = both branches): ' + ''.join(
             {'zero': 'z', 'cond': 'c', 'guided': 'G'}[k] for k in pipe.last_guidance_plan))
+    if getattr(pipe, 'last_window_plan', None) is not None:
+        logging.info(f'context windows: {len(pipe.last_window_plan)} windows per step, starting at latent frames {pipe.last_window_plan}')
     if rank == 0:
         if args.save_file is None:
             args.save_file = default_save_name(args)

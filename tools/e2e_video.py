@@ -11,6 +11,8 @@ usage: python tools/e2e_video.py [--workload 1080p|720p] [--steps 50] [--solver 
 --steps entries — `CS` = every other step.
 --guide_interval LO,HI / --cfg_zero_star / --cfg_zero_init N / --guide_rescale PHI (opt-in guidance options): the launcher's flags; the
 line then carries the median wall time of the 'guided', 'cond' and 'zero' steps separately.
+--frame_num N / --context_frames N / --context_overlap M / --context_fuse pyramid|flat (opt-in context windows): a clip longer than one DiT
+pass through the launcher's flags; the line then carries the window starts.
 """
 import argparse
 import json
@@ -56,7 +58,16 @@ def main():
     ap.add_argument('--cfg_zero_star', action='store_true', help="CFG-Zero*'s projection in the guided steps")
     ap.add_argument('--cfg_zero_init', type=int, default=0, metavar='N', help='the first N steps predict zero')
     ap.add_argument('--guide_rescale', type=float, default=0.0, metavar='PHI', help='guidance rescale in [0, 1]')
+    # the launcher's context-window flags
+    ap.add_argument('--frame_num', type=int, default=81, help='frames of the clip (4n+1)')
+    ap.add_argument('--context_frames', type=int, default=None, metavar='N', help='context windows of N frames (4n+1)')
+    ap.add_argument('--context_overlap', type=int, default=16, metavar='M', help='frames two neighbouring windows share')
+    ap.add_argument('--context_fuse', default='pyramid', choices=['pyramid', 'flat'])
     args = ap.parse_args()
+    extra = {}
+    if args.context_frames is not None:
+        from wan.utils.context_windows import ContextWindows
+        extra['windows'] = ContextWindows(frames=args.context_frames, overlap=args.context_overlap, fuse=args.context_fuse)
     guidance = None
     if args.guide_interval is not None or args.cfg_zero_star or args.cfg_zero_init or args.guide_rescale:
         from wan.utils.guidance import Guidance
@@ -108,16 +119,16 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     start.record()
-    video = pipe.generate(prompt, size=size, frame_num=81, sampling_steps=args.steps, sample_solver=args.solver, n_prompt=negative, seed=42,
-                          offload_model=True, callback=callback, step_cache=step_cache, **({} if guidance is None else {'guidance': guidance}))
+    video = pipe.generate(prompt, size=size, frame_num=args.frame_num, sampling_steps=args.steps, sample_solver=args.solver, n_prompt=negative, seed=42,
+                          offload_model=True, callback=callback, step_cache=step_cache, **({} if guidance is None else {'guidance': guidance}), **extra)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     t1 = time.perf_counter()
     frames = video_frames_uint8(video[None])
     torch.cuda.synchronize()
     u8_s = time.perf_counter() - t1
-    assert tuple(video.shape) == (3, 81, size[1], size[0]) and torch.isfinite(video).all().item()
-    assert frames.dtype == torch.uint8 and tuple(frames.shape) == (81, size[1], size[0], 3)
+    assert tuple(video.shape) == (3, args.frame_num, size[1], size[0]) and torch.isfinite(video).all().item()
+    assert frames.dtype == torch.uint8 and tuple(frames.shape) == (args.frame_num, size[1], size[0], 3)
     step_ms = [a.elapsed_time(b) for a, b in zip([start] + marks[:-1], marks)]
     mid = sorted(step_ms[1:])[len(step_ms[1:]) // 2] if len(step_ms) > 1 else step_ms[0]
     plan = pipe.last_step_plan
@@ -130,9 +141,11 @@ def main():
         by_kind.update({f'median_{k}_step_ms': med([m for m, kk in list(zip(step_ms, kinds))[1:] if kk == k]) for k in ('guided', 'cond', 'zero')})
         by_kind.update({'guidance': repr(guidance), 'guidance_plan': ''.join({'zero': 'z', 'cond': 'c', 'guided': 'G'}[k] for k in kinds),
                         'step_ms': [round(m, 1) for m in step_ms]})
+    if pipe.last_window_plan is not None:
+        by_kind.update({'windows': repr(extra['windows']), 'window_starts': pipe.last_window_plan})
     line = {'what':'WanT2V.generate end to end (tools/e2e_video.py): text encoder x 2 prompts + %d denoising steps (two guidance branches through WanModel.forward_pair, CFG 5.0, %s) '
                     '+ WanVAE.decode, offload_model=True (the reference default), one call on the wall clock' % (args.steps, args.solver),
-            'workload': '14B T2V %dx%dx81f' % size, 'sampling_steps': args.steps,
+            'workload': '14B T2V %dx%dx%df' % (size + (args.frame_num,)), 'sampling_steps': args.steps,
             'step_cache': args.step_cache, **by_kind, 'steps_computed': sum(pipe.last_step_plan) if pipe.last_step_plan is not None else args.steps, 'sec_per_video_measured': wall,
             'first_step_ms_incl_text_encoder_and_prompt_caches': step_ms[0], 'median_later_step_ms': mid, 'sum_steps_s': sum(step_ms) / 1e3,
             'after_last_step_s_vae_decode_and_teardown': wall - sum(step_ms) / 1e3, 'uint8_frames_s_not_included': u8_s,
