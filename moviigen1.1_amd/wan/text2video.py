@@ -12,7 +12,6 @@ of `[len<=512, 4096]` tensors, and `input_prompt` / `n_prompt` may also be pre-c
 """
 import contextlib
 import gc
-import inspect
 import logging
 import math
 import os
@@ -28,7 +27,8 @@ from .modules.vae import WanVAE
 from .utils.fm_solvers import FlowDPMSolverMultistepScheduler, get_sampling_sigmas, retrieve_timesteps
 from .utils.fm_solvers_unipc import FlowUniPCMultistepScheduler
 from .utils.context_windows import ContextWindows
-from .utils.guidance import Guidance, adjust_step_plan
+from .utils.guidance import Guidance
+from .utils.sample_plan import refuse_windows_with_step_cache, sample_plan
 from .utils.step_cache import resolve_plan
 
 
@@ -61,6 +61,11 @@ def _checked_windows(windows):
     return windows
 
 
+def dit_seq_len(frames, h, w, patch_size, sp_size):
+    """the DiT's seq_len for a latent [C, frames, h, w]: its tokens, rounded up to a multiple of the sequence-parallel degree"""
+    return math.ceil((h * w) / (patch_size[1] * patch_size[2]) * frames / sp_size) * sp_size
+
+
 class WindowRun:
     """what a `generate` call with context windows allocates once and every step reuses: the plan (a WindowPlan), the gather buffer `lat`
     [C, Fw, h, w], the whole-clip predictions `cond` and `uncond` [C, F, h, w] (uncond: None when no step of the call runs both branches),
@@ -73,7 +78,31 @@ class WindowRun:
         self.cond = torch.empty_like(latent)
         self.uncond = torch.empty_like(latent) if both else None
         self.w, self.first = plan.weights.to(latent.device), plan.first.to(latent.device)
-        self.seq_len = math.ceil((h * w) / (patch_size[1] * patch_size[2]) * plan.Fw / sp_size) * sp_size
+        self.seq_len = dit_seq_len(plan.Fw, h, w, patch_size, sp_size)
+
+
+class GuidedMix:
+    """the mix of a call's 'guided' steps, built once per call: the effective guide scale (the Guidance's when it has one, else the call's
+    `guide_scale`) and, only when the three-launch form will run (CFG-Zero* or rescale on, and some step is 'guided'), its scratch: the five
+    fp64 sums `stats`, the per-workgroup `partials` and the two fp32 coefficients `coef`.  mix(out, uncond, cond) -> out, no host read."""
+
+    def __init__(self, guidance, guide_scale, any_guided, device):
+        self.scale = guide_scale if guidance is None or guidance.scale is None else guidance.scale
+        self.guidance = guidance
+        self.stats = self.partials = self.coef = None
+        if guidance is not None and not guidance.plain_mix and any_guided:
+            self.stats = torch.empty(5, dtype=torch.float64, device=device)
+            self.partials = ops.cfg_stats_partials(device)
+            self.coef = torch.empty(2, dtype=torch.float32, device=device)
+
+    def __call__(self, out, uncond, cond):
+        if self.stats is None:          # the reference's u + g (c - u)
+            ops.cfg_combine(out, uncond, cond, self.scale)
+        else:                           # CFG-Zero* / rescale: five fp64 sums, two coefficients, the mix
+            ops.cfg_stats(uncond, cond, self.stats, self.partials)
+            ops.cfg_coefficients(self.stats, out.numel(), self.scale, self.guidance.zero_star, self.guidance.rescale, self.coef)
+            ops.cfg_combine_coef(out, uncond, cond, self.coef)
+        return out
 
 
 class WanT2V:
@@ -235,6 +264,15 @@ class WanT2V:
             ops.window_blend(run.cond, cond, f0, run.w[k], run.first[k])
         return run.cond, None if context_null is None else run.uncond
 
+    def _predictions(self, kind, latent, t, context, context_null, seq_len, wrun):
+        """(cond, uncond) of a 'guided' step, (cond, None) of a 'cond' step — the one call the sampling loop makes for a forward; wrun: the
+        call's WindowRun, None = the whole latent in one pass"""
+        if wrun is not None:
+            return self._window_predictions(wrun, latent, t, context, context_null if kind == 'guided' else None)
+        if kind == 'guided':
+            return self._guidance_pair(latent, t, context, context_null, seq_len)
+        return self._cond_prediction(latent, t, context, seq_len), None
+
     def _scheduler(self, sample_solver, sampling_steps, shift):
         """-> (scheduler, timesteps on the device) of the reference's two solvers (text2video.py:186-207)"""
         if sample_solver == 'unipc':
@@ -343,8 +381,13 @@ class WanT2V:
             unchanged: init_video, strength and `inpaint` work at any length.  The buffers and the device copies of the weights are
             allocated once per call; no host read in the loop.  Not together with a step cache (its residuals would be per window):
             ValueError before any forward."""
-        return self._sample(input_prompt, size, frame_num, shift, sample_solver, sampling_steps, guide_scale, n_prompt, seed, offload_model,
-                            noise, callback, step_cache, guidance, windows, init_video, strength, edit=None)
+        return self._sample(input_prompt=input_prompt, size=size, frame_num=frame_num, shift=shift, sample_solver=sample_solver,
+                            sampling_steps=sampling_steps, guide_scale=guide_scale, n_prompt=n_prompt, seed=seed, offload_model=offload_model,
+                            noise=noise, callback=callback, step_cache=step_cache, guidance=guidance, windows=windows,
+                            init_video=init_video, strength=strength)
+
+    # `generate`'s arguments behind input_prompt with their defaults: what `inpaint` takes as keywords
+    _GENERATE_DEFAULTS = dict(zip(generate.__code__.co_varnames[2:generate.__code__.co_argcount], generate.__defaults__))
 
     def masked_edit(self, init_video, mask, keep_frames, size, frame_num):
         """`inpaint`'s mask / keep_frames -> MaskedEdit(pm, lm): the mask through the cover / crop geometry of the frames (ops.mask_from_u8), the
@@ -393,31 +436,32 @@ class WanT2V:
         mask gives the bits of `generate(init_video=, strength=)`."""
         if init_video is None:
             raise ValueError('inpaint needs init_video: there is nothing to keep')
-        args = inspect.signature(self.generate).bind(input_prompt, init_video=init_video, strength=strength, **kw)
-        args.apply_defaults()
-        edit = self.masked_edit(init_video, mask, keep_frames, args.arguments['size'], args.arguments['frame_num'])
-        return self._sample(edit=edit, **args.arguments)
+        for name in kw:
+            if name not in self._GENERATE_DEFAULTS:
+                raise TypeError(f"inpaint() got an unexpected keyword argument '{name}'")
+        args = dict(self._GENERATE_DEFAULTS, **kw, input_prompt=input_prompt, init_video=init_video, strength=strength)
+        return self._sample(edit=self.masked_edit(init_video, mask, keep_frames, args['size'], args['frame_num']), **args)
 
-    def _sample(self, input_prompt, size, frame_num, shift, sample_solver, sampling_steps, guide_scale, n_prompt, seed, offload_model,
-                noise, callback, step_cache, guidance, windows, init_video, strength, edit):
-        """the body of `generate` and `inpaint`; edit: None, or inpaint's MaskedEdit"""
+    def _sample(self, *, input_prompt, size, frame_num, shift, sample_solver, sampling_steps, guide_scale, n_prompt, seed, offload_model,
+                noise, callback, step_cache, guidance, windows, init_video, strength, edit=None):
+        """the body of `generate` and `inpaint`, which hand it `generate`'s arguments by name; edit: None, or inpaint's MaskedEdit.
+        Three parts: the arguments resolved and checked (no GPU), the tensors and the call's SamplePlan, the loop over plan.steps."""
+        step_cache = self.step_cache if step_cache is None else step_cache
         guidance = _checked_guidance(self.guidance if guidance is None else guidance)
         windows = _checked_windows(self.windows if windows is None else windows)
         n_run, i0 = v2v_steps(sampling_steps, strength)
         if init_video is None and i0:
             raise ValueError('strength < 1 needs init_video: there is nothing to start from')
-        F = frame_num
-        target_shape = (self.vae.model.z_dim, (F - 1) // self.vae_stride[0] + 1, size[1] // self.vae_stride[1],
+        target_shape = (self.vae.model.z_dim, (frame_num - 1) // self.vae_stride[0] + 1, size[1] // self.vae_stride[1],
                         size[0] // self.vae_stride[2])
-        seq_len = math.ceil((target_shape[2] * target_shape[3]) / (self.patch_size[1] * self.patch_size[2]) *
-                            target_shape[1] / self.sp_size) * self.sp_size
+        seq_len = dit_seq_len(*target_shape[1:], self.patch_size, self.sp_size)
         wplan = None                # the context windows of this call: a function of the latent's length alone; None = one pass, the loop as it was
         if windows is not None:
             if windows.stride != self.vae_stride[0]:
                 raise ValueError(f'windows: {windows!r} counts frames for a temporal VAE stride of {windows.stride}, this pipeline has {self.vae_stride[0]}')
             wplan = windows.plan(target_shape[1])
-        if wplan is not None and (self.step_cache if step_cache is None else step_cache) is not None:
-            raise ValueError('windows cannot be combined with step_cache: the cached residuals would be per window (not built); pass step_cache=None')
+        window_starts = None if wplan is None else wplan.starts
+        refuse_windows_with_step_cache(window_starts, step_cache)       # (ahead of the prompt encoder; sample_plan checks the resolved plan again)
         if isinstance(n_prompt, str) and n_prompt == "":
             n_prompt = self.sample_neg_prompt
         seed = seed if seed >= 0 else random.randint(0, sys.maxsize)
@@ -444,57 +488,30 @@ class WanT2V:
             if next(self.model.parameters()).device != self.device:     # only after a real offload (a no-op move would
                 self.model.to(self.device)                               # still drop the fused-weight views: 28 GB re-packed)
             noise_pred = torch.empty_like(latent)
-            plan, plan_stats = resolve_plan(self.step_cache if step_cache is None else step_cache, self.model, timesteps, i0)
-            kinds = mix = None          # the guidance plan, one of 'zero' | 'cond' | 'guided' per schedule index; None: every step 'guided'
-            if guidance is not None:
-                kinds = guidance.plan(sigmas_host[:len(timesteps_host)], i0)
-                if guidance.scale is not None:
-                    guide_scale = guidance.scale
-                if plan is not None:    # residuals are per context (a rank's own branch only under cfg_parallel): wan/utils/guidance.py
-                    plan = adjust_step_plan(plan, kinds, i0, own_branch_only=self.cfgp is not None)
-                if not guidance.plain_mix and 'guided' in kinds[i0:]:      # the scratch of the three-launch mix, once per call
-                    mix = (torch.empty(5, dtype=torch.float64, device=self.device), ops.cfg_stats_partials(self.device),
-                           torch.empty(2, dtype=torch.float32, device=self.device))
-            self.last_guidance_plan = kinds
-            self.last_window_plan = None if wplan is None else list(wplan.starts)
-            wrun = None                 # buffers and device arrays of the windowed steps, once per call
-            if wplan is not None:
-                wrun = WindowRun(wplan, latent, kinds is None or 'guided' in kinds[i0:], self.patch_size, self.sp_size)
-            self.last_step_plan = plan
-            self.last_step_timesteps = timesteps if plan is not None else None     # what the plan was made of (tools/step_cache_calibrate.py)
-            for i, t_host in enumerate(timesteps_host[i0:], start=i0):
+            step_plan, stats = resolve_plan(step_cache, self.model, timesteps, i0)
+            kinds = None if guidance is None else guidance.plan(sigmas_host[:len(timesteps_host)], i0)
+            # every decision that depends on the schedule alone, made here once: wan/utils/sample_plan.py
+            plan = sample_plan(len(timesteps_host), i0, kinds, step_plan, stats, own_branch_only=self.cfgp is not None, window_starts=window_starts)
+            self.last_guidance_plan, self.last_step_plan, self.last_window_plan = plan.kinds, plan.step_plan, plan.window_starts
+            self.last_step_timesteps = timesteps if plan.step_plan is not None else None     # what the plan was made of (tools/step_cache_calibrate.py)
+            # scratch and buffers of the guided mix and of the windowed steps, once per call
+            mix = GuidedMix(guidance, guide_scale, plan.any_guided, self.device)
+            wrun = None if wplan is None else WindowRun(wplan, latent, plan.any_guided, self.patch_size, self.sp_size)
+            for i, kind, cache in plan.steps:
                 t = timesteps[i:i + 1]
-                kind = 'guided' if kinds is None else kinds[i]
-                step_mode = contextlib.nullcontext()
-                if plan is not None and not plan[i]:
-                    step_mode = self.model.step_cache('skip')
-                elif plan is not None and (plan_stats or (i + 1 < len(plan) and not plan[i + 1])):
-                    # a computed step keeps its residual only when the next step adds it again (or the calibration tool asked for the sums)
-                    step_mode = self.model.step_cache('compute', stats=plan_stats)
-                pred = noise_pred
                 if kind == 'zero':          # CFG-Zero*'s zero-init: no forward, the scheduler steps on a zero prediction
-                    noise_pred.zero_()
-                elif kind == 'cond':        # outside the guidance interval: the conditional branch alone, its prediction as it is (a new
-                    with step_mode:         # tensor of every forward)
-                        pred = (self._cond_prediction(latent, t, context, seq_len) if wrun is None else
-                                self._window_predictions(wrun, latent, t, context, None)[0])
-                else:
-                    with step_mode:
-                        cond, uncond = (self._guidance_pair(latent, t, context, context_null, seq_len) if wrun is None else
-                                        self._window_predictions(wrun, latent, t, context, context_null))
-                    if mix is None:
-                        ops.cfg_combine(noise_pred, uncond, cond, guide_scale)
-                    else:                   # CFG-Zero* / rescale: five fp64 sums, two coefficients, the mix: no host read
-                        ops.cfg_stats(uncond, cond, mix[0], mix[1])
-                        ops.cfg_coefficients(mix[0], noise_pred.numel(), guide_scale, guidance.zero_star, guidance.rescale, mix[2])
-                        ops.cfg_combine_coef(noise_pred, uncond, cond, mix[2])
-                latent = sample_scheduler.step(pred.unsqueeze(0), t_host, latent.unsqueeze(0),
+                    pred = noise_pred.zero_()
+                else:                       # a 'cond' step's prediction is used as it is (a new tensor of every forward)
+                    with self.model.step_cache(cache, stats=plan.stats) if cache else contextlib.nullcontext():     # (a 'skip' scope reads no stats)
+                        cond, uncond = self._predictions(kind, latent, t, context, context_null, seq_len, wrun)
+                    pred = cond if kind == 'cond' else mix(noise_pred, uncond, cond)
+                latent = sample_scheduler.step(pred.unsqueeze(0), timesteps_host[i], latent.unsqueeze(0),
                                                return_dict=False, generator=seed_g)[0].squeeze(0)
                 if edit is not None:        # the step left the latent at sigma_{i+1}: put the kept cells back at that noise level
                     ops.masked_renoise(latent, edit.z0, noise, edit.lm, 1.0 - sigmas_host[i + 1], sigmas_host[i + 1])
                 if callback is not None:
                     callback(i, latent)
-            if plan is not None:
+            if plan.step_plan is not None:
                 self.model.drop_step_cache()
             videos = self._decode([latent], target_shape, offload_model)
             if edit is not None and videos is not None:     # on the rank that holds the video: kept pixels are the source's, bit for bit

@@ -745,3 +745,107 @@ def test_mp4_mjpeg_container(tmp_path):
             M.write_mp4_mjpeg(str(tmp_path / 'bad.mp4'), bad)
     with pytest.raises(ValueError):
         M.write_mp4_mjpeg(str(tmp_path / 'bad.mp4'), frames, fps=0)
+
+
+# ------------------------------------------------------------------------------------------------
+# wan/utils/sample_plan.py: the plan of one generate / inpaint call
+# ------------------------------------------------------------------------------------------------
+def _parent_loop_steps(n, i0, kinds, plan, stats, own_branch_only):
+    """what the sampling loop decided PER STEP before the plan existed, condition for condition: the step-cache plan adjusted to the guidance
+    kinds behind both, then for every i the kind, and the model.step_cache scope that was built from plan[i], plan[i + 1] and stats and
+    ENTERED only by the two branches that run a forward -> ([(i, kind, scope entered)], adjusted plan)"""
+    from wan.utils.guidance import adjust_step_plan
+    if kinds is not None and plan is not None:
+        plan = adjust_step_plan(plan, kinds, i0, own_branch_only=own_branch_only)
+    steps = []
+    for i in range(i0, n):
+        kind = 'guided' if kinds is None else kinds[i]
+        step_mode = None
+        if plan is not None and not plan[i]:
+            step_mode = 'skip'
+        elif plan is not None and (stats or (i + 1 < len(plan) and not plan[i + 1])):
+            step_mode = 'compute'
+        steps.append((i, kind, None if kind == 'zero' else step_mode))
+    return steps, plan
+
+
+def test_sample_plan_equals_the_per_step_conditions_exhaustively():
+    import itertools
+    from wan.utils.sample_plan import sample_plan
+    cases = 0
+    for n in range(1, 6):
+        all_kinds = [None] + [list(k) for k in itertools.product(('zero', 'cond', 'guided'), repeat=n)]
+        for i0 in range(n):
+            all_plans = [None]
+            for p in itertools.product((True, False), repeat=n):
+                all_plans.append(list(p[:i0]) + [True] + list(p[i0 + 1:]))      # resolve_plan: the first step that runs is computed
+            for kinds, plan, stats, own in itertools.product(all_kinds, all_plans, (False, True), (False, True)):
+                want_steps, want_plan = _parent_loop_steps(n, i0, kinds, plan, stats, own)
+                asked = None if plan is None else list(plan)
+                got = sample_plan(n, i0, kinds, plan, stats, own_branch_only=own)
+                assert got.steps == want_steps and got.step_plan == want_plan, (n, i0, kinds, plan, stats, own)
+                assert plan == asked                                                        # the caller's list is not written
+                assert got.any_guided == any(k == 'guided' for _, k, _ in want_steps) and got.stats == stats
+                cases += 1
+    assert cases == 186816
+
+
+def test_sample_plan_literal_cases():
+    from wan.utils.sample_plan import sample_plan
+    z, c, G, C, S = 'zero', 'cond', 'guided', True, False
+    kinds = [c, c, G, G, G, c]
+    # step 2, the first 'guided' step behind 'cond' steps, is computed; a computed step keeps its residual only in front of a skipped one
+    p = sample_plan(6, 0, kinds, [C, S, S, C, S, C])
+    assert p.step_plan == [C, S, C, C, S, C] and p.kinds == kinds and p.any_guided and not p.stats
+    assert p.steps == [(0, c, 'compute'), (1, c, 'skip'), (2, G, None), (3, G, 'compute'), (4, G, 'skip'), (5, c, None)]
+    # stats: every computed step captures
+    p = sample_plan(6, 0, kinds, [C, S, S, C, S, C], stats=True)
+    assert [s[2] for s in p.steps] == ['compute', 'skip', 'compute', 'compute', 'skip', 'compute'] and p.stats
+    # cfg-parallel groups: the 'cond' step behind 'guided' ones is computed too
+    p = sample_plan(6, 0, kinds, [C, S, S, S, S, S], own_branch_only=True)
+    assert p.step_plan == [C, S, C, S, S, C] and [s[2] for s in p.steps] == ['compute', 'skip', 'compute', 'skip', 'skip', None]
+    # no Guidance: every step 'guided', the plan as resolve_plan gave it; video-to-video from index 3: three steps
+    p = sample_plan(6, 3, None, [C, S, C, C, C, S])
+    assert p.kinds is None and p.step_plan == [C, S, C, C, C, S] and p.steps == [(3, G, None), (4, G, 'compute'), (5, G, 'skip')]
+    # 'zero' steps run no forward and enter no scope, whatever the plan says; the first step that runs one is computed
+    p = sample_plan(4, 0, [z, z, G, c], [C, S, S, S])
+    assert p.step_plan == [C, S, C, S] and p.steps == [(0, z, None), (1, z, None), (2, G, 'compute'), (3, c, 'skip')]
+    # no step cache, and no guided step at or behind i0: nothing needs the unconditional buffers
+    p = sample_plan(3, 1, [G, c, c])
+    assert p.step_plan is None and p.steps == [(1, c, None), (2, c, None)] and not p.any_guided
+    assert sample_plan(2, 0).steps == [(0, G, None), (1, G, None)] and sample_plan(2, 0).any_guided
+
+
+def test_sample_plan_published_views():
+    from wan.utils.context_windows import ContextWindows
+    from wan.utils.sample_plan import sample_plan
+    p = sample_plan(4, 0)
+    assert p.kinds is None and p.step_plan is None and p.window_starts is None
+    cw = ContextWindows(frames=9, overlap=4)
+    assert cw.plan(2) is None                                                   # the clip fits one window: no window plan, the loop as it was
+    starts = cw.plan(7).starts
+    p = sample_plan(4, 0, window_starts=starts)
+    assert p.window_starts == [0, 2, 4] and isinstance(p.window_starts, list) and p.window_starts is not starts
+    with pytest.raises(ValueError) as e:
+        sample_plan(4, 0, step_plan=[True] * 4, window_starts=starts)
+    assert str(e.value) == 'windows cannot be combined with step_cache: the cached residuals would be per window (not built); pass step_cache=None'
+    assert sample_plan(4, 0, step_plan=[True] * 4).step_plan == [True] * 4      # each alone is fine
+
+
+def test_sample_plan_imports_without_the_backend(tmp_path):
+    """the module and what it imports, alone in a package tree that has neither wan.backend nor the library file: a fresh process imports and
+    runs it, and neither torch nor the backend was loaded"""
+    import shutil
+    utils = tmp_path / 'wan' / 'utils'
+    utils.mkdir(parents=True)
+    for d in (tmp_path / 'wan', utils):
+        (d / '__init__.py').write_text('')
+    for name in ('sample_plan.py', 'guidance.py'):
+        shutil.copy(os.path.join(ROOT, 'moviigen1.1_amd', 'wan', 'utils', name), utils / name)
+    code = ("import sys; from wan.utils.sample_plan import sample_plan; "
+            "assert 'torch' not in sys.modules and 'wan.backend' not in sys.modules and 'numpy' not in sys.modules; "
+            "print(sample_plan(2, 0, ['cond', 'cond'], [True, False]).steps)")
+    env = {k: v for k, v in os.environ.items() if k != 'PYTHONPATH'}
+    r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, cwd=str(tmp_path), env=dict(env, PYTHONPATH=str(tmp_path)))
+    assert r.returncode == 0, r.stderr
+    assert r.stdout.strip() == "[(0, 'cond', 'compute'), (1, 'cond', 'skip')]"

@@ -15,6 +15,7 @@ line then carries the median wall time of the 'guided', 'cond' and 'zero' steps 
 pass through the launcher's flags; the line then carries the window starts.
 """
 import argparse
+import importlib.util
 import json
 import os
 import sys
@@ -26,6 +27,16 @@ sys.path.insert(0, os.path.join(ROOT, 'moviigen1.1_amd'))
 sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden'))
 
 import torch  # noqa: E402
+
+SAMPLING_FLAGS = ('--guide_interval', '--cfg_zero_star', '--cfg_zero_init', '--guide_rescale', '--context_frames', '--context_overlap', '--context_fuse')
+
+
+def _launcher():
+    """scripts/inference/generate.py as a module: the one definition of the sampling flags (FLAGS, _guidance_spec, _windows_spec)"""
+    spec = importlib.util.spec_from_file_location('mg_generate_launcher', os.path.join(ROOT, 'scripts', 'inference', 'generate.py'))
+    module = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(module)
+    return module
 
 
 class WordHashTokenizer:
@@ -53,26 +64,15 @@ def main():
     ap.add_argument('--prompt-words', type=int, default=511)
     ap.add_argument('--neg-words', type=int, default=129)
     ap.add_argument('--step_cache', default=None, help='threshold, or a plan of C / S letters repeated over the steps (CS = every other step)')
-    # the launcher's guidance flags (scripts/inference/generate.py)
-    ap.add_argument('--guide_interval', default=None, metavar='LO,HI', help='both guidance branches only while sigma lies in [LO, HI]')
-    ap.add_argument('--cfg_zero_star', action='store_true', help="CFG-Zero*'s projection in the guided steps")
-    ap.add_argument('--cfg_zero_init', type=int, default=0, metavar='N', help='the first N steps predict zero')
-    ap.add_argument('--guide_rescale', type=float, default=0.0, metavar='PHI', help='guidance rescale in [0, 1]')
-    # the launcher's context-window flags
     ap.add_argument('--frame_num', type=int, default=81, help='frames of the clip (4n+1)')
-    ap.add_argument('--context_frames', type=int, default=None, metavar='N', help='context windows of N frames (4n+1)')
-    ap.add_argument('--context_overlap', type=int, default=16, metavar='M', help='frames two neighbouring windows share')
-    ap.add_argument('--context_fuse', default='pyramid', choices=['pyramid', 'flat'])
+    # the launcher's guidance and context-window (3.9) flags: its definitions, its validation
+    launcher = _launcher()
+    for flag, kw in launcher.FLAGS:
+        if flag in SAMPLING_FLAGS:
+            ap.add_argument(flag, **kw)
     args = ap.parse_args()
-    extra = {}
-    if args.context_frames is not None:
-        from wan.utils.context_windows import ContextWindows
-        extra['windows'] = ContextWindows(frames=args.context_frames, overlap=args.context_overlap, fuse=args.context_fuse)
-    guidance = None
-    if args.guide_interval is not None or args.cfg_zero_star or args.cfg_zero_init or args.guide_rescale:
-        from wan.utils.guidance import Guidance
-        interval = tuple(float(v) for v in args.guide_interval.split(',')) if args.guide_interval is not None else (0.0, 1.0)
-        guidance = Guidance(interval=interval, zero_star=args.cfg_zero_star, zero_init_steps=args.cfg_zero_init, rescale=args.guide_rescale)
+    guidance, windows = launcher._guidance_spec(args), launcher._windows_spec(args)
+    extra = {} if windows is None else {'windows': windows}
     step_cache = None
     if args.step_cache is not None:
         pat = args.step_cache.upper()
