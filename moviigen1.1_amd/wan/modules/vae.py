@@ -11,7 +11,8 @@ Execution: activations are channels-last [T][H][W][C] fp32 on the device; every 
 exact-f32 MFMA (mg_vae_conv_f32) with the causal cache, the zero padding, the 2x upsample, the
 bias and the residual add folded in; RMS_norm+SiLU and the per-frame d=384 attention are HIP
 kernels as well.  The chunked decode with its 2-frame feature cache follows the reference
-protocol (vae.py:101-141,202-220,423-472,544-568) slot for slot.
+protocol (vae.py:101-141,202-220,423-472,544-568) convolution for convolution:
+each cached convolution keeps its tail under its own parameter name (`_Run.cache`).
 
 The encoder (Encoder3d, WanVAE_.encode) reuses all of that and adds what the decoder has no counterpart of: the
 down-samplers' 3x3 convolution of stride 2 behind a one-sided zero pad and their 3x1x1 temporal convolution of stride 2
@@ -31,11 +32,38 @@ from ..backend import ops
 __all__ = ['WanVAE']
 
 CACHE_T = 2
+_REP = object()      # cache entry of a temporal up-sampler behind the first chunk, which skips time_conv (reference vae.py:106-108: 'Rep')
 
 _MEAN = [-0.7571, -0.7089, -0.9113, 0.1075, -0.1745, 0.9653, -0.1517, 1.5508,
          0.4134, -0.0715, 0.5517, -0.3632, -0.1922, -0.9497, 0.2503, -0.2921]
 _STD = [2.8184, 1.4541, 2.3275, 2.6558, 1.2196, 1.7708, 2.6052, 2.0743,
         3.2687, 2.1526, 2.8652, 1.5579, 1.6382, 1.1253, 2.8251, 1.9160]
+
+
+def _causal_tail(prev, x, zero_pad=False):
+    """what a causal convolution remembers behind the chunk x [T,...]: the last CACHE_T frames of [previous chunks | x], given the tail `prev`
+    remembered so far (reference vae.py:205-214).  zero_pad: with no previous tail a zero frame stands in for the missing frame (the 'Rep' case
+    of the temporal up-samplers, vae.py:116-121)."""
+    if x.shape[0] >= CACHE_T:
+        return x[-CACHE_T:].clone()
+    if prev is not None:
+        return torch.cat([prev[-1:], x[-1:]], dim=0)
+    if zero_pad:
+        return torch.cat([torch.zeros_like(x[-1:]), x[-1:]], dim=0)
+    return x[-1:].clone()
+
+
+def _last_frame(x):
+    """what the stride-2 time_conv of a temporal down-sampler remembers: one frame (it reads [last frame of the previous chunk | the chunk])."""
+    return x[-1:].clone()
+
+
+class _Run:
+    """what one decode / encode call carries from chunk to chunk: `cache`, the tail of every causal convolution under the convolution's
+    parameter prefix ('decoder.middle.0.residual.2', ...), and `band`, this rank's column band in decode_spatial (None elsewhere)."""
+
+    def __init__(self, band=None):
+        self.cache, self.band = {}, band
 
 
 class _Band:
@@ -51,7 +79,6 @@ class _Band:
         self.group, self.P, self.rank = group, P, rank
         self.left = rank - 1 if rank > 0 else None
         self.right = rank + 1 if rank < P - 1 else None
-        self.scale = 1                     # 2x per spatial up-sampler passed
         self.halo_bytes = 0                # what this rank sent as halos (reported by tools/bench_vae.py)
 
     def halo(self, x):
@@ -85,7 +112,8 @@ class _Band:
         """t [T,H,Wl,K] (this band) -> [T,H,W,K] of all bands in image order, on every rank (the attention block's keys / values)."""
         from ..distributed import collectives
         T, H, Wl, K = t.shape
-        ws = [w * self.scale for w in self.widths]
+        scale = Wl // self.widths[self.rank]                # 2x per spatial up-sampler passed
+        ws = [w * scale for w in self.widths]
         wmax = max(ws)
         mine = t.new_zeros(T, H, wmax, K)
         mine[:, :, :Wl].copy_(t)
@@ -139,12 +167,9 @@ class WanVAE_:
         for i in range(n_up):
             pre = f'decoder.upsamples.{i}.'
             self.layout.append(('up' if (pre + 'resample.1.weight') in self.P else 'res', pre))
-        self.n_slots = sum(1 for k, v in self.P.items()
-                           if k.startswith('decoder.') and k.endswith('weight') and v.dim() == 5 and
-                           'resample' not in k and 'to_qkv' not in k and 'proj' not in k)
+        self.n_slots = sum(len(s[2]) for s in self._stages())          # the decoder's cached convolutions
         self.mean = torch.tensor(_MEAN[:z_dim], dtype=torch.float32, device=self.device)
         self.inv_std = (1.0 / torch.tensor(_STD[:z_dim], dtype=torch.float32)).to(self.device)
-        self._band = None                  # set for the duration of a decode_spatial call: this rank's column band
         # the encoder half, when the state dict has it (n_slots, layout and _stages() above are decoder quantities)
         n_down = 1 + max([int(k.split('.')[2]) for k in self.P if k.startswith('encoder.downsamples.')], default=-1)
         self.enc_layout = []
@@ -157,63 +182,57 @@ class WanVAE_:
     def _new(self, *shape):
         return torch.empty(*shape, dtype=torch.float32, device=self.device)
 
-    def _conv(self, name, x, cache=None, up2=False, residual=None):
+    def _conv(self, name, x, cache=None, up2=False, residual=None, halo=None):
+        """one convolution launch.  halo = (col0, cols) in the W-band decode: x carries its neighbours' border columns, this band's `cols`
+        columns start at column col0 of it and are what is computed (mg_vae_conv_cols_f32)."""
         w = self.P[name + '.weight']
         kt, kh, kw = w.shape[1:4]
         T, H, W, _ = x.shape
-        out = self._new(T, 2 * H if up2 else H, 2 * W if up2 else W, w.shape[0])
-        return ops.vae_conv(x, w, self.P[name + '.bias'], out, kt, kh, kw, cache=cache, up2=up2, residual=residual,
-                            mode=self._conv_mode)
+        if halo is None:
+            out = self._new(T, 2 * H if up2 else H, 2 * W if up2 else W, w.shape[0])
+            return ops.vae_conv(x, w, self.P[name + '.bias'], out, kt, kh, kw, cache=cache, up2=up2, residual=residual,
+                                mode=self._conv_mode)
+        col0, cols = halo
+        return ops.vae_conv_cols(x, w, self.P[name + '.bias'], self._new(T, H, cols, w.shape[0]), kt, kh, kw, col0,
+                                 cache=cache, residual=residual, mode=self._conv_mode)
 
-    def _cached_conv(self, name, x, cache, idx, residual=None):
+    def _cached_conv(self, name, x, run, residual=None):
         """the feat_cache protocol of every 3x3x3 conv (reference vae.py:205-217)."""
-        i = idx[0]
-        prev = cache[i]
-        col0 = None
-        if self._band is not None:
+        prev = run.cache.get(name)
+        halo = None
+        if run.band is not None:
             # W-band decode: the convolution reads one column across each cut — fetch the neighbours' border columns first; the causal cache
             # keeps the frames WITH their halos (so nothing is exchanged twice)
             cols = x.shape[2]
-            x, col0 = self._band.halo(x)
-        if x.shape[0] >= CACHE_T:
-            cx = x[-CACHE_T:].clone()
-        elif prev is not None:
-            cx = torch.cat([prev[-1:], x[-1:]], dim=0)
-        else:
-            cx = x[-1:].clone()
-        if col0 is None:
-            out = self._conv(name, x, cache=prev, residual=residual)
-        else:
-            w = self.P[name + '.weight']
-            kt, kh, kw = w.shape[1:4]
-            out = ops.vae_conv_cols(x, w, self.P[name + '.bias'], self._new(x.shape[0], x.shape[1], cols, w.shape[0]), kt, kh, kw, col0,
-                                    cache=prev, residual=residual, mode=self._conv_mode)
-        cache[i] = cx
-        idx[0] += 1
+            x, col0 = run.band.halo(x)
+            halo = (col0, cols)
+        cx = _causal_tail(prev, x)
+        out = self._conv(name, x, cache=prev, residual=residual, halo=halo)
+        run.cache[name] = cx             # the previous tail goes only now: the convolution that reads it is enqueued
         return out
 
     def _norm_silu(self, x, gamma, silu=True):
         return ops.vae_rmsnorm_silu(x, self.P[gamma], self._new(*x.shape), silu)
 
-    def _res(self, pre, x, cache, idx):
+    def _res(self, pre, x, run):
         h = x
         if (pre + 'shortcut.weight') in self.P:
             h = self._conv(pre + 'shortcut', x)
         y = self._norm_silu(x, pre + 'residual.0.gamma')
-        y = self._cached_conv(pre + 'residual.2', y, cache, idx)
+        y = self._cached_conv(pre + 'residual.2', y, run)
         y = self._norm_silu(y, pre + 'residual.3.gamma')
-        return self._cached_conv(pre + 'residual.6', y, cache, idx, residual=h)
+        return self._cached_conv(pre + 'residual.6', y, run, residual=h)
 
-    def _attn(self, pre, x):
+    def _attn(self, pre, x, band=None):
         T, H, W, C = x.shape
         L = H * W
         y = self._norm_silu(x, pre + 'norm.gamma', silu=False)
         qkv = self._conv(pre + 'to_qkv', y)
         a = self._new(T, H, W, C)
-        if self._band is not None:
+        if band is not None:
             # W-band decode: queries = this band's pixels, keys / values = every band's (one all-gather of k|v per chunk); a row's result does
             # not depend on which rows are computed with it (mg_vae_attn_rows_f32)
-            kv = self._band.gather_cols(qkv[..., C:])
+            kv = band.gather_cols(qkv[..., C:])
             Lk = kv.shape[1] * kv.shape[2]
             ws = self._new(ops.vae_attn_workspace_floats(Lk, C))
             ops.vae_attn_rows(qkv.view(T, L, 3 * C)[..., :C], kv.view(T, Lk, 2 * C), a.view(T, L, C), ws)
@@ -222,27 +241,22 @@ class WanVAE_:
         ops.vae_attn(qkv.view(T, L, 3 * C), a.view(T, L, C), ws)
         return self._conv(pre + 'proj', a, residual=x)
 
-    def _up(self, pre, x, cache, idx):
+    def _up(self, pre, x, run):
         if (pre + 'time_conv.weight') in self.P:       # upsample3d (reference vae.py:103-137)
-            i = idx[0]
-            if cache[i] is None:
-                cache[i] = 'Rep'
-                idx[0] += 1
+            prev = run.cache.get(pre + 'time_conv')
+            if prev is None:
+                run.cache[pre + 'time_conv'] = _REP
             else:
-                rep = isinstance(cache[i], str)
-                if x.shape[0] >= CACHE_T:
-                    cx = x[-CACHE_T:].clone()
-                elif rep:
-                    cx = torch.cat([torch.zeros_like(x[-1:]), x[-1:]], dim=0)
-                else:
-                    cx = torch.cat([cache[i][-1:], x[-1:]], dim=0)
-                y = self._conv(pre + 'time_conv', x, cache=None if rep else cache[i])
-                cache[i] = cx
-                idx[0] += 1
+                if prev is _REP:
+                    prev = None
+                cx = _causal_tail(prev, x, zero_pad=True)
+                y = self._conv(pre + 'time_conv', x, cache=prev)
+                run.cache[pre + 'time_conv'] = cx
+                del prev                                 # the old tail is free for the allocations below, as it was when a list held it
                 T, H, W, C2 = y.shape
                 x = ops.vae_time_interleave(y, self._new(2 * T, H, W, C2 // 2))
         if self.upconv == 'gather':
-            if self._band is not None:
+            if run.band is not None:
                 raise NotImplementedError("decode_spatial runs the up-sampling convolutions as phase convolutions (upconv='phases')")
             return self._conv(pre + 'resample.1', x, up2=True)
         name = pre + 'resample.1'
@@ -250,14 +264,13 @@ class WanVAE_:
         if wp is None:                                   # folded once per checkpoint
             wp = self.P[name + '.phases'] = ops.vae_upconv_fold_weights(self.P[name + '.weight'])
         T, H, W, _ = x.shape
-        if self._band is not None:
-            xh, col0 = self._band.halo(x)
-            self._band.scale *= 2
+        if run.band is not None:
+            xh, col0 = run.band.halo(x)
             return ops.vae_upconv_phases_cols(xh, wp, self.P[name + '.bias'], self._new(T, 2 * H, 2 * W, wp.shape[1]), col0, mode=self._conv_mode)
         return ops.vae_upconv_phases(x, wp, self.P[name + '.bias'], self._new(T, 2 * H, 2 * W, wp.shape[1]), mode=self._conv_mode)
 
     # ---- the encoder (reference Encoder3d.forward, Resample downsample2d / downsample3d, WanVAE_.encode) ----------------
-    def _down(self, pre, x, cache, idx):
+    def _down(self, pre, x, run):
         """Resample, down-sampling: per frame a 3x3 convolution of stride 2 behind a zero pad of (0 before, 1 behind) on H and W; downsample3d then
         a 3x1x1 convolution of stride 2 in time over [last frame of the previous chunk | the chunk], no temporal padding — the first chunk (one
         frame) passes through and is remembered."""
@@ -266,40 +279,33 @@ class WanVAE_:
         shp = ops.vae_conv_strided_out_shape(x.shape, (1, 3, 3), (1, 2, 2), 0, (0, 1), (0, 1))
         y = ops.vae_conv_strided(x, w, self.P[name + '.bias'], self._new(*shp, w.shape[0]), (1, 2, 2), 0, (0, 1), (0, 1), mode=ops.VAE_EXACT)
         if (pre + 'time_conv.weight') in self.P:
-            i = idx[0]
-            keep = y[-1:].clone()
-            if cache[i] is not None:
+            prev = run.cache.get(pre + 'time_conv')
+            keep = _last_frame(y)
+            if prev is not None:
                 wt = self.P[pre + 'time_conv.weight']
                 shp = ops.vae_conv_strided_out_shape(y.shape, (3, 1, 1), (2, 1, 1), 1, (0, 0), (0, 0))
-                y = ops.vae_conv_strided(y, wt, self.P[pre + 'time_conv.bias'], self._new(*shp, wt.shape[0]), (2, 1, 1), 1, cache=cache[i],
+                y = ops.vae_conv_strided(y, wt, self.P[pre + 'time_conv.bias'], self._new(*shp, wt.shape[0]), (2, 1, 1), 1, cache=prev,
                                          mode=ops.VAE_EXACT)
-            cache[i] = keep
-            idx[0] += 1
+            run.cache[pre + 'time_conv'] = keep
         return y
 
-    def _encoder_chunk(self, video, t0, n, cache):
+    def _encoder_chunk(self, video, t0, n, run):
         """Encoder3d.forward on the frames [t0, t0 + n) of video [3,T,H,W] -> [n', H/8, W/8, 2 z_dim] channels-last."""
         _, _, H, W = video.shape
         xs = ops.vae_video_in(video, t0, n, self._new(n, H, W + 2, 4))          # only the chunk is ever staged
-        prev = cache[0]                                                        # the feat_cache protocol of _cached_conv, on staged frames
-        if n >= CACHE_T:
-            cx = xs[-CACHE_T:].clone()
-        elif prev is not None:
-            cx = torch.cat([prev[-1:], xs[-1:]], dim=0)
-        else:
-            cx = xs[-1:].clone()
+        prev = run.cache.get('encoder.conv1')                                  # the feat_cache protocol of _cached_conv, on staged frames
+        cx = _causal_tail(prev, xs)
         w = self.P['encoder.conv1.weight']
         x = ops.vae_conv_in3(xs, w, self.P['encoder.conv1.bias'], self._new(n, H, W, w.shape[0]), cache=prev, mode=ops.VAE_EXACT)
-        cache[0] = cx
+        run.cache['encoder.conv1'] = cx
         del xs, prev
-        idx = [1]
         for kind, pre in self.enc_layout:
-            x = self._res(pre, x, cache, idx) if kind == 'res' else self._down(pre, x, cache, idx)
-        x = self._res('encoder.middle.0.', x, cache, idx)
+            x = self._res(pre, x, run) if kind == 'res' else self._down(pre, x, run)
+        x = self._res('encoder.middle.0.', x, run)
         x = self._attn('encoder.middle.1.', x)
-        x = self._res('encoder.middle.2.', x, cache, idx)
+        x = self._res('encoder.middle.2.', x, run)
         x = self._norm_silu(x, 'encoder.head.0.gamma')
-        return self._cached_conv('encoder.head.2', x, cache, idx)
+        return self._cached_conv('encoder.head.2', x, run)
 
     @torch.no_grad()
     def encode(self, x):
@@ -315,44 +321,57 @@ class WanVAE_:
             raise ValueError(f'encode expects a video tensor [3, T >= 1, H >= 8, W >= 8], got {tuple(x.shape) if torch.is_tensor(x) else type(x)}')
         x = x.to(self.device, torch.float32).contiguous()
         T = x.shape[1]
-        cache = [None] * (sum(1 for k, v in self.P.items() if k.startswith('encoder.') and k.endswith('weight') and v.dim() == 5) + 8)
+        run = _Run()
         outs = []
         for i in range(1 + (T - 1) // 4):
-            outs.append(self._encoder_chunk(x, 0, 1, cache) if i == 0 else self._encoder_chunk(x, 1 + 4 * (i - 1), 4, cache))
+            outs.append(self._encoder_chunk(x, 0, 1, run) if i == 0 else self._encoder_chunk(x, 1 + 4 * (i - 1), 4, run))
         y = self._conv('conv1', torch.cat(outs, dim=0) if len(outs) > 1 else outs[0])           # [T', h, w, 2 z_dim]: mu | log_var
         return ops.vae_latent_out(y, self.mean, self.inv_std, self._new(self.z_dim, *y.shape[:3]))
 
-    # ---- the decoder as a list of stages (each owns a contiguous range of feat_cache slots) ---------
+    # ---- the decoder as a list of stages (each owns the caches of its own convolutions) ---------
     def _stages(self):
-        """[(kind, prefix, cache slots used)] in execution order (reference Decoder3d.forward, vae.py:423-472)."""
-        st = [('conv1', 'decoder.conv1', 1), ('res', 'decoder.middle.0.', 2), ('attn', 'decoder.middle.1.', 0),
-              ('res', 'decoder.middle.2.', 2)]
+        """[(kind, prefix, names of the stage's cached convolutions)] in execution order (reference Decoder3d.forward, vae.py:423-472)."""
+        def res(pre):
+            return ('res', pre, (pre + 'residual.2', pre + 'residual.6'))
+        st = [('conv1', 'decoder.conv1', ('decoder.conv1',)), res('decoder.middle.0.'), ('attn', 'decoder.middle.1.', ()), res('decoder.middle.2.')]
         for kind, pre in self.layout:
-            st.append((kind, pre, 2 if kind == 'res' else (1 if (pre + 'time_conv.weight') in self.P else 0)))
-        st.append(('head', 'decoder.head.', 1))
+            st.append(res(pre) if kind == 'res' else ('up', pre, (pre + 'time_conv',) if (pre + 'time_conv.weight') in self.P else ()))
+        st.append(('head', 'decoder.head.', ('decoder.head.2',)))
         return st
 
-    def _run_stage(self, stage, x, cache, idx):
+    def _run_stage(self, stage, x, run):
         kind, pre, _ = stage
         if kind == 'conv1':
-            return self._cached_conv(pre, x, cache, idx)
+            return self._cached_conv(pre, x, run)
         if kind == 'res':
-            return self._res(pre, x, cache, idx)
+            return self._res(pre, x, run)
         if kind == 'attn':
-            return self._attn(pre, x)
+            return self._attn(pre, x, run.band)
         if kind == 'up':
-            return self._up(pre, x, cache, idx)
+            return self._up(pre, x, run)
         x = self._norm_silu(x, 'decoder.head.0.gamma')
-        return self._cached_conv('decoder.head.2', x, cache, idx)
+        return self._cached_conv('decoder.head.2', x, run)
 
-    def _decoder_chunk(self, x, cache, first=0, last=None):
-        """stages [first, last) on one chunk; `cache` is the full feat_cache list (a rank only ever
-        touches the slots of its own stages)."""
-        stages = self._stages()
-        idx = [sum(s[2] for s in stages[:first])]
-        for stage in stages[first:len(stages) if last is None else last]:
-            x = self._run_stage(stage, x, cache, idx)
+    def _decoder_chunk(self, x, run, first=0, last=None):
+        """stages [first, last) on one chunk; run.cache only ever gets the entries of these stages' convolutions (a pipeline rank's own)."""
+        for stage in self._stages()[first:last]:
+            x = self._run_stage(stage, x, run)
         return x
+
+    def _decode_chunks(self, z, chunks, run):
+        """z [C,T,H,W] on the device (the latent, or this rank's band of it) -> its video [3, 1+4(T-1), 8H, 8W], chunk by chunk."""
+        C, T, H, W = z.shape
+        x = ops.vae_latent_in(z, self.mean, self.inv_std, self._new(T, H, W, C))
+        x = self._conv('conv2', x)                                  # 1x1x1: no halo
+        video = self._new(3, 1 + 4 * (T - 1), 8 * H, 8 * W)
+        t0, f0 = 0, 0
+        for n in chunks:
+            y = self._decoder_chunk(x[t0:t0 + n], run)
+            ops.vae_video_out(y, video, f0)
+            t0 += n
+            f0 += y.shape[0]
+        assert f0 == video.shape[1] and y.shape[2] == 8 * W
+        return video
 
     def stage_costs(self, h, w):
         """MACs per steady-state chunk (one latent frame) of every stage at latent size h x w — the
@@ -383,25 +402,12 @@ class WanVAE_:
 
     def _decode(self, z, chunks=None):
         z = z.to(self.device, torch.float32).contiguous()
-        C, T, H, W = z.shape
-        x = ops.vae_latent_in(z, self.mean, self.inv_std, self._new(T, H, W, C))
-        x = self._conv('conv2', x)
         # The reference decodes ONE latent frame per decoder call (vae.py:555-566) to bound its peak memory (2.45 GB per
         # activation at 832x1920); the cache protocol makes any chunking of frames 1.. give the same values (SURVEY
         # Appendix A; tests: chunked == unchunked).  With 288 GB of HBM the engine decodes 4 latent frames per call: the
         # low-resolution stages then launch enough tiles to fill 256 CUs (9.77 vs 10.16 s at 1920x832, peak 45 GB).
         # MOVIIGEN_VAE_CHUNK=1 restores the reference's chunking.
-        chunks = self._chunks(T, chunks)
-        cache = [None] * (self.n_slots + 8)
-        video = self._new(3, 1 + 4 * (T - 1), 8 * H, 8 * W)
-        t0, f0 = 0, 0
-        for n in chunks:
-            y = self._decoder_chunk(x[t0:t0 + n], cache)
-            ops.vae_video_out(y, video, f0)
-            t0 += n
-            f0 += y.shape[0]
-        assert f0 == video.shape[1]
-        return video
+        return self._decode_chunks(z, self._chunks(z.shape[1], chunks), _Run())
 
     def _chunks(self, T, chunks=None):
         """the latent-frame chunking of a decode: frame 0 alone (the 'Rep' protocol of the temporal up-samplers needs it),
@@ -465,24 +471,7 @@ class WanVAE_:
         C, T, H, W = z.shape
         band = _Band(group, P, rank, W)
         c0, wl = band.starts[rank], band.widths[rank]
-        chunks = self._chunks(T, chunks)
-        self._band = band
-        try:
-            zb = z[:, :, :, c0:c0 + wl].contiguous()
-            x = ops.vae_latent_in(zb, self.mean, self.inv_std, self._new(T, H, wl, C))
-            x = self._conv('conv2', x)                                  # 1x1x1: no halo
-            cache = [None] * (self.n_slots + 8)
-            mine = self._new(3, 1 + 4 * (T - 1), 8 * H, 8 * wl)         # this band of the video
-            t0, f0 = 0, 0
-            for n in chunks:
-                band.scale = 1
-                y = self._decoder_chunk(x[t0:t0 + n], cache)
-                ops.vae_video_out(y, mine, f0)
-                t0 += n
-                f0 += y.shape[0]
-            assert f0 == mine.shape[1] and band.scale == 8
-        finally:
-            self._band = None
+        mine = self._decode_chunks(z[:, :, :, c0:c0 + wl].contiguous(), self._chunks(T, chunks), _Run(band))      # this band of the video
         self.last_halo_bytes = band.halo_bytes
         if rank != 0:
             collectives.send(mine, 0 if group is None else dist.get_global_rank(group, 0), group)
@@ -524,7 +513,7 @@ class WanVAE_:
         first, last = cuts[seg], cuts[seg + 1]
         src = dist.get_global_rank(group, rank + 1) if group is not None else rank + 1      # upstream: segment seg-1
         dst = dist.get_global_rank(group, rank - 1) if group is not None else rank - 1      # downstream: segment seg+1
-        cache = [None] * (self.n_slots + 8)
+        run = _Run()
         video = self._new(3, 1 + 4 * (T - 1), 8 * H, 8 * W) if seg == nseg - 1 else None
         cuda = self.device.type == 'cuda'
         cur = torch.cuda.current_stream(self.device) if cuda else None
@@ -556,7 +545,7 @@ class WanVAE_:
                     x.record_stream(cur)
                 if ci + 1 < len(chunks):
                     nxt = post_recv(ci + 1)                # in flight while this chunk computes
-            y = self._decoder_chunk(x, cache, first, last)
+            y = self._decoder_chunk(x, run, first, last)
             if video is not None:
                 ops.vae_video_out(y, video, f0)
                 f0 += y.shape[0]

@@ -740,19 +740,87 @@ def test_vae_decode_vs_reference(dev, golden, dim, t):
 def test_vae_modules_vs_oracle(dev, golden):
     """AttentionBlock and Resample pieces against the reference's module outputs."""
     import wan
+    from wan.modules.vae import _Run
     g = golden('g5_vae_d8_t3')
     vae = wan.modules.WanVAE(state_dict=W.make_vae_params(8, 1), device=dev).model
     x = _cl(T(g['conv_x'])).to(dev)
     assert scale_err(vae._attn('decoder.middle.1.', x), _cl(T(g['attn']))) < 1e-5
-    cache = [None, None]
-    o1 = vae._res('decoder.middle.0.', x[:1], cache, [0])
-    o2 = vae._res('decoder.middle.0.', x[1:], cache, [0])
+    run = _Run()
+    o1 = vae._res('decoder.middle.0.', x[:1], run)
+    o2 = vae._res('decoder.middle.0.', x[1:], run)
     assert scale_err(torch.cat([o1, o2]), _cl(T(g['res_chunked']))) < 1e-5
     xu = _cl(T(g['up_x'])).to(dev)
-    cache = [None]
+    run = _Run()
     for i in range(3):
-        o = vae._up('decoder.upsamples.3.', xu[i:i + 1], cache, [0])
+        o = vae._up('decoder.upsamples.3.', xu[i:i + 1], run)
         assert scale_err(o, _cl(T(g[f'up_c{i}']))) < 1e-5, i
+
+
+@pytest.fixture(scope='module')
+def vae_walk(dev):
+    """the tiny decoder walked over all stages on two one-frame chunks [1,4,6,16] with one cache: the model, the chunks, the two
+    outputs and the cache as it stood behind each chunk (the entries are never written in place: a shallow copy is a snapshot)."""
+    import wan
+    from wan.modules.vae import _Run
+    m = wan.modules.WanVAE(state_dict=W.make_vae_params(8, 1), device=dev).model
+    xs = [W.randn((1, 4, 6, 16), 51 + i).to(dev) for i in range(2)]
+    run, outs, caches = _Run(), [], []
+    for x in xs:
+        outs.append(m._decoder_chunk(x, run))
+        caches.append(dict(run.cache))
+    return m, xs, outs, caches
+
+
+@pytest.mark.gpu
+def test_vae_cache_by_name(vae_walk):
+    """what a decode leaves in its cache: one entry per cached convolution, under the convolution's name, in execution order; behind
+    the first chunk one frame each and the first-chunk marker for every time_conv; behind a second one-frame chunk two frames each.  A
+    time_conv that was fed ONE frame then (the first temporal up-sampler's) keeps [zero frame | that frame]: the zero frame stands in for
+    the skipped first chunk.  The second up-sampler's is fed the TWO frames the first made of the chunk and keeps those, as the reference
+    does (no frame is missing, nothing is padded)."""
+    from wan.modules.vae import _REP, _Run
+    m, xs, outs, (c1, c2) = vae_walk
+    st = m._stages()
+    names = [n for s in st for n in s[2]]
+    tc = [n for n in names if n.endswith('time_conv')]
+    assert len(tc) == 2 and list(c1) == names and list(c2) == names
+    for n in names:
+        if n in tc:
+            assert c1[n] is _REP
+        else:
+            assert torch.is_tensor(c1[n]) and c1[n].shape[0] == 1, n
+        assert torch.is_tensor(c2[n]) and c2[n].shape[0] == 2, n
+    fed = []
+    for n in tc:                                 # what the time_conv read in the second chunk: the stages in front of it, on the first chunk's cache
+        run = _Run()
+        run.cache.update(c1)
+        xin = m._decoder_chunk(xs[1], run, 0, next(i for i, s in enumerate(st) if n in s[2]))
+        fed.append(xin.shape[0])
+        if xin.shape[0] == 1:
+            assert not c2[n][0].any().item() and xin.any().item() and torch.equal(c2[n][1:], xin), n
+        else:
+            assert torch.equal(c2[n], xin[-2:]), n
+    assert fed == [1, 2]
+    assert tuple(outs[0].shape) == (1, 32, 48, 3) and tuple(outs[1].shape) == (4, 32, 48, 3)
+
+
+@pytest.mark.gpu
+def test_vae_cache_splits_at_a_stage_cut(vae_walk):
+    """the property decode_pipelined relies on: stages [0, k) on one empty cache and [k, end) on another, fed the first part's output,
+    give the bits of the uncut walk on both chunks, and the two caches hold disjoint names that together are all of them — at a cut
+    in the middle of the list and on either side of the first temporal up-sampler."""
+    from wan.modules.vae import _Run
+    m, xs, outs, _ = vae_walk
+    st = m._stages()
+    names = {n for s in st for n in s[2]}
+    up = next(i for i, s in enumerate(st) if s[2] and s[0] == 'up')
+    for k in sorted({len(st) // 2, up, up + 1}):
+        a, b = _Run(), _Run()
+        for x, want in zip(xs, outs):
+            y = m._decoder_chunk(m._decoder_chunk(x, a, 0, k), b, k)
+            assert torch.equal(y, want), k
+        assert a.cache and b.cache and not set(a.cache) & set(b.cache) and set(a.cache) | set(b.cache) == names, k
+        assert set(a.cache) == {n for s in st[:k] for n in s[2]}, k
 
 
 # ------------------------------------------------------------------------------------------------

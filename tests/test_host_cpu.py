@@ -340,6 +340,50 @@ def test_vae_pipeline_host_logic():
     assert partition_costs(wts, 3)[0] == 0 and partition_costs(wts, 3)[-1] == n
 
 
+@pytest.mark.parametrize('chunking', [(1, 1, 1, 1), (1, 4, 4, 1), (1, 2, 1, 3), (3, 1)])
+def test_vae_causal_tail(chunking):
+    """the one cache rule of the VAE's causal convolutions: after every chunk the tail is the last min(2, frames so far) frames of
+    everything fed so far — frames [T,1,1,1] whose values are their (1-based) numbers —, a copy and not a view, and what the oracle keeps."""
+    from oracle.vae import _next_cache
+    from wan.modules.vae import CACHE_T, _causal_tail
+    frames = torch.arange(1, sum(chunking) + 1, dtype=torch.float32).reshape(-1, 1, 1, 1)
+    prev = oprev = None
+    t0 = 0
+    for n in chunking:
+        x = frames[t0:t0 + n]
+        t0 += n
+        padded = _causal_tail(prev, x, zero_pad=True)
+        if prev is None and n == 1:                                  # the 'Rep' case: a zero frame stands in for the missing one
+            assert padded.flatten().tolist() == [0.0, x.item()]
+        tail = _causal_tail(prev, x)
+        assert torch.equal(tail, frames[max(0, t0 - CACHE_T):t0]), (chunking, t0)
+        assert tail.untyped_storage().data_ptr() != frames.untyped_storage().data_ptr()
+        if prev is not None or n > 1:                                # zero_pad matters only where a frame is missing
+            assert torch.equal(padded, tail)
+        otail = _next_cache(x.permute(1, 0, 2, 3)[None], oprev)       # the oracle's layout: [1,C,T,H,W]
+        assert torch.equal(otail[0].permute(1, 0, 2, 3), tail)
+        prev, oprev = tail, otail
+
+
+def test_vae_stage_cache_names():
+    """the third field of a _stages() entry: the parameter prefixes of the stage's cached convolutions — unique, each a convolution of
+    temporal extent 3, together every such convolution of the decoder, and per kind as many as the stage runs."""
+    from wan.modules.vae import WanVAE_
+    v = WanVAE_(W.make_vae_params(8, 1), device='cpu')
+    st = v._stages()
+    names = [n for s in st for n in s[2]]
+    assert len(set(names)) == len(names) == v.n_slots > 0
+    for n in names:
+        w = v.P[n + '.weight']                                       # repacked [Cout,kt,kh,kw,Cin]
+        assert w.dim() == 5 and w.shape[1] == 3, n
+    assert set(names) == {k[:-len('.weight')] for k, w in v.P.items()
+                          if k.startswith('decoder.') and k.endswith('.weight') and w.dim() == 5 and w.shape[1] == 3}
+    for kind, pre, ns in st:
+        want = {'conv1': 1, 'head': 1, 'res': 2, 'attn': 0, 'up': int((pre + 'time_conv.weight') in v.P)}[kind]
+        assert isinstance(ns, tuple) and len(ns) == want, (kind, pre, ns)
+    assert sorted(len(s[2]) for s in st if s[0] == 'up') == [0, 1, 1]
+
+
 def test_collectives_have_one_test_transport_guard():
     """every RCCL call of the product lives in wan/distributed/collectives.py, and the host-staged gloo transport of the
     one-GPU multi-process tests is reachable through exactly one predicate."""

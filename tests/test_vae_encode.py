@@ -79,6 +79,7 @@ def test_decoder_only_state_dict_constructs_and_encode_names_missing_keys():
         m.encode(torch.zeros(3, 5, 16, 16))
     full = WanVAE_(_params(8), device='cpu')
     assert full.n_slots == m.n_slots and full.layout == m.layout and full._stages() == m._stages() and not full.enc_missing
+    assert [s[2] for s in full._stages()] == [s[2] for s in m._stages()] and all(isinstance(s[2], tuple) for s in m._stages())
     assert [k for k, _ in full.enc_layout] == ['res', 'res', 'down', 'res', 'res', 'down', 'res', 'res', 'down', 'res', 'res']
     for bad in (torch.zeros(3, 0, 16, 16), torch.zeros(3, 5, 7, 16), torch.zeros(4, 5, 16, 16), torch.zeros(3, 16, 16)):
         with pytest.raises(ValueError, match='encode expects'):

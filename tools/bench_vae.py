@@ -236,10 +236,10 @@ if args.stages:
     m = vae.model
     ev, orig = [], m._run_stage
 
-    def timed(stage, x, cache, idx):
+    def timed(stage, x, run):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        y = orig(stage, x, cache, idx)
+        y = orig(stage, x, run)
         b.record()
         ev.append((a, b))
         return y
