@@ -598,6 +598,31 @@ int mg_vae_latent_out_f32(const float* x, int ldx, const float* mean, const floa
 int mg_lora_merge(void* w, int w_f32, int64_t ldw, int N, int K, const float* up, int64_t ldu, const float* down, int64_t ldd, int R,
                   void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Normalized attention guidance (WanModel.forward(nag=); not the reference's arithmetic, opt-in).
+ * A pure addition to ABI 9.
+ * ---------------------------------------------------------------------------------------- */
+
+/* The row-wise mix of two cross-attention outputs (Chen et al. 2025, NAG): zp [rows][dim] is the output for the positive prompt, zn for
+ * the negative one, both bf16 with all heads of a token in one row (row strides ldp / ldn elements).  Per row, every operation in fp32:
+ *   g_j  = fma(scale, p_j, -((scale - 1) n_j))
+ *   Np   = sum_j |p_j|,  Ng = sum_j |g_j|        (the norm is over the whole row, not per head)
+ *   c    = tau Np / (Ng + 1e-7)  if Ng > tau Np,  else 1
+ *   out_j = bf16( fma(alpha c, g_j, (1 - alpha) p_j) )                      ONE rounding to bf16
+ * The comparison form divides by nothing that can be 0: Np = 0 < Ng gives c = 0, both sums 0 give out = 0.
+ * One wave owns a row: a lane adds its elements in index order (chunk lane + 64 i, i ascending, 8 elements each), the 64 partial sums
+ * meet in a fixed xor butterfly — the bits of a row depend on the row and the three parameters alone, not on rows, the grid or the
+ * rows that share the launch.  No atomics, no device memory besides the operands.
+ * scale = 1 gives out == zp bit for bit, and so does zn == zp (finite inputs): the fp32 value lies within ~2 scale 2^-24 relative of
+ * the bf16 number p_j, far inside bf16's half ulp for every scale <= 64.
+ * out may be zp itself (same pointer, ldo == ldp: a wave reads its whole row before it stores); it may not overlap zn, or zp otherwise.
+ * MG_ERR_ARG: a null pointer; scale < 1 or > 64, tau < 1, alpha outside [0, 1], any of them not finite; out overlapping an input other
+ *   than as above (the address ranges [ptr, ptr + (rows - 1) ld + dim) are compared).
+ * MG_ERR_SHAPE: dim <= 0, dim % 8, dim > 8192, an ld % 8 or < dim, rows < 0, a pointer not 16-byte aligned.
+ * rows == 0 with valid arguments: MG_OK, nothing is launched. */
+int mg_nag_combine_bf16(const uint16_t* zp, int64_t ldp, const uint16_t* zn, int64_t ldn, uint16_t* out, int64_t ldo, int64_t rows, int dim,
+                        float scale, float tau, float alpha, void* stream);
+
 #ifdef MG_AB_BUILD
 /* ------------------------------------------------------------------------------------------
  * A/B LIBRARY ONLY (libmoviigen_hip_ab.so, built from the same sources with -DMG_AB_BUILD; the product library

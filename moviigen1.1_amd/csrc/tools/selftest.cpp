@@ -205,6 +205,38 @@ static void test_rmsnorm_rope(int rows, int dim, int hd, int F, int H, int W, in
     report(nm, err, 6e-2);
 }
 
+// mg_nag_combine_bf16 against the header's arithmetic in double; row 0: zn == zp (the result is zp), row 1: zp == 0 (the result is 0)
+static void test_nag_combine(int rows, int dim, float s, float tau, float alpha, bool in_place) {
+    auto p = randbf((size_t)rows * dim, 2.f), n = randbf((size_t)rows * dim, 2.f);
+    for (int j = 0; j < dim; ++j) n[j] = p[j];
+    if (rows > 1) for (int j = 0; j < dim; ++j) p[(size_t)dim + j] = 0;
+    Dev<uint16_t> dp(p), dn(n), dout((size_t)rows * dim);
+    uint16_t* o = in_place ? dp.p : dout.p;
+    int rc = mg_nag_combine_bf16(dp.p, dim, dn.p, dim, o, dim, rows, dim, s, tau, alpha, 0);
+    CK(hipDeviceSynchronize());
+    auto got = in_place ? dp.host() : dout.host();
+    double err = rc ? 1e9 : 0;
+    for (int r = 0; r < rows; ++r) {
+        double np = 0, ng = 0;
+        for (int j = 0; j < dim; ++j) {
+            const double pj = bf2f(p[(size_t)r * dim + j]), nj = bf2f(n[(size_t)r * dim + j]);
+            np += fabs(pj);
+            ng += fabs(s * pj - (s - 1.0) * nj);
+        }
+        const double c = ng > tau * np ? tau * np / (ng + 1e-7) : 1.0;
+        for (int j = 0; j < dim; ++j) {
+            const double pj = bf2f(p[(size_t)r * dim + j]), nj = bf2f(n[(size_t)r * dim + j]);
+            const double ref = alpha * c * (s * pj - (s - 1.0) * nj) + (1.0 - alpha) * pj;
+            const double g = bf2f(got[(size_t)r * dim + j]);
+            err = fmax(err, fabs(g - ref) / fmax(1.0, fabs(ref)));         // bf16: 2^-9 relative, + fp32 noise
+            if (r < 2 && got[(size_t)r * dim + j] != p[(size_t)r * dim + j] && !(r == 1 && g == 0.0)) err = 1e9;
+        }
+    }
+    char nm[128];
+    snprintf(nm, sizeof nm, "nag_combine r%d d%d s=%g tau=%g a=%g inplace=%d", rows, dim, s, tau, alpha, (int)in_place);
+    report(nm, err, 4e-3);
+}
+
 static void test_pack(int64_t L, int heads) {
     const int64_t nt = (L + 63) / 64;
     const int ldv = heads * 128 * 3;  // strided like a fused QKV buffer
@@ -1011,6 +1043,8 @@ int main(int argc, char** argv) {
     test_rmsnorm_rope(25, 5120, 128, 2, 5, 5, 25, true);  // SP rank slice
     test_rmsnorm_rope(17, 128, 32, 1, 4, 4, 0, true);
     test_rmsnorm_rope(33, 5120, 128, 1, 1, 1, 0, false);
+    test_nag_combine(33, 5120, 4.f, 2.5f, 0.5f, false);
+    test_nag_combine(9, 136, 11.f, 1.2f, 1.0f, true);
     test_pack(300, 2);
     test_pack(64, 1);
 

@@ -86,6 +86,7 @@ SIGNATURES = {
     'mg_window_gather_f32': [c_vp, c_int, c_i64, c_i64, c_i64, c_int, c_vp, c_vp],
     'mg_window_blend_f32': [c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp],
     'mg_lora_merge': [c_vp, c_int, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_int, c_vp],
+    'mg_nag_combine_bf16': [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_f32, c_f32, c_f32, c_vp],
     'mg_comm_unique_id': [c_vp],
     'mg_comm_create': [c_vp, c_int, c_int, c_vp],
     'mg_comm_destroy': [c_vp],

@@ -440,6 +440,29 @@ def cfg_combine_coef(out, uncond, cond, coef):
     return out
 
 
+def nag_combine(zp, zn, out, scale, tau, alpha):
+    """out [rows, dim] bf16 <- the normalized-attention-guidance mix of the cross-attention outputs zp (positive prompt) and zn (negative
+    prompt), per row: g = scale zp - (scale - 1) zn, clipped to tau times zp's L1 norm, blended with zp by alpha (include/moviigen_hip.h,
+    DESIGN.md 3.11).  Row strides are free (multiples of 8); out may be zp itself, not zn.  1 <= scale <= 64, tau >= 1, 0 <= alpha <= 1."""
+    _chk_rows(zp, torch.bfloat16, 'zp'); _chk_rows(zn, torch.bfloat16, 'zn'); _chk_rows(out, torch.bfloat16, 'out')
+    if tuple(zn.shape) != tuple(zp.shape) or tuple(out.shape) != tuple(zp.shape):
+        raise lib.MoviigenHipError(f'nag_combine shape mismatch zp{tuple(zp.shape)} zn{tuple(zn.shape)} out{tuple(out.shape)}')
+    rows, dim = zp.shape
+    if dim < 8 or dim % 8 or dim > 8192:
+        raise lib.MoviigenHipError(f'nag_combine: dim must be a multiple of 8 in [8, 8192], got {dim}')
+    for name, t in (('zp', zp), ('zn', zn), ('out', out)):
+        if t.stride(0) % 8 or (rows == 1 and t.stride(0) < dim):
+            raise lib.MoviigenHipError(f'nag_combine: {name} needs a row stride that is a multiple of 8 and >= dim, got {t.stride(0)}')
+        _chk_aligned16(t, name)
+    scale, tau, alpha = float(scale), float(tau), float(alpha)
+    if not (1.0 <= scale <= 64.0 and 1.0 <= tau < float('inf') and 0.0 <= alpha <= 1.0):
+        raise lib.MoviigenHipError(f'nag_combine: 1 <= scale <= 64, 1 <= tau < inf, 0 <= alpha <= 1; got {scale}, {tau}, {alpha}')
+    if rows == 0:
+        return out
+    lib.call('mg_nag_combine_bf16', _p(zp), zp.stride(0), _p(zn), zn.stride(0), _p(out), out.stride(0), rows, dim, scale, tau, alpha, _st())
+    return out
+
+
 # ---- umT5 encoder glue ---------------------------------------------------------------------------
 def embed_rows(table, ids, out):
     """out [n, dim] = table [vocab, dim][ids [n]] (ids clamped to the table): dense bf16 / int64 tensors, dim a multiple of 8."""

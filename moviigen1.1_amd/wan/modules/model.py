@@ -584,15 +584,21 @@ class WanModel(nn.Module):
         """what names a prompt tensor: the key of _context()'s cache and of the step cache's residuals"""
         return (ctx.data_ptr(), tuple(ctx.shape), ctx._version)
 
-    def _step_resid(self, ws, ctx, create):
-        """the residual buffer of this workspace for prompt tensor `ctx` (zeros when new: r_old of a first computed step), or None"""
+    def _resid_key(self, ctx, nag=None):
+        """what names a forward's residual in the step cache: the prompt tensor, and under NAG the negative prompt tensor and
+        (scale, tau, alpha) too — a plain forward and a NAG forward of one prompt never share a residual"""
         key = self._ctx_key(ctx)
+        return key if nag is None else (key, self._ctx_key(nag[1]), nag[0].params)
+
+    def _step_resid(self, ws, ctx, create, nag=None):
+        """the residual buffer of this workspace for prompt tensor `ctx` (zeros when new: r_old of a first computed step), or None"""
+        key = self._resid_key(ctx, nag)
         table = ws.setdefault('resid', {})
         hit = table.get(key)
         if hit is None and create:
             if len(table) >= 4:         # as _context(): prompts come and go, [L, dim] fp32 each does not pile up
                 table.pop(next(iter(table)))
-            hit = table[key] = (ctx, torch.zeros_like(ws['x']))      # (ctx is kept alive so that its data_ptr stays unique)
+            hit = table[key] = ((ctx, nag), torch.zeros_like(ws['x']))      # (the prompts are kept alive so that their data_ptr stays unique)
         return None if hit is None else hit[1]
 
     def time_embeddings(self, timesteps):
@@ -782,31 +788,42 @@ class WanModel(nn.Module):
                 ws['x0'] = torch.empty_like(x)
             ws['x0'].copy_(x)
 
-    def _block_cross_attn(self, i, blk, plan, lin, ctx_emb, ctx_layers):
-        """x += cross_attn(norm3(x), text): the text keys / values are made the first time block i meets this prompt"""
+    def _block_cross_attn(self, i, blk, plan, lin, ctx_emb, ctx_layers, nag=None):
+        """x += cross_attn(norm3(x), text): the text keys / values are made the first time block i meets this prompt.
+        nag: None, or (NAG, emb, layers) of the negative prompt: the attention runs a second time with the negative
+        prompt's K/V — made and cached like the prompt's — into ws['q'] (the un-normed q projection there is dead behind norm_rope_qk),
+        and ops.nag_combine mixes the two results per token in ws['a'], in front of the unchanged `o` projection."""
         ws, x, ca = plan.ws, plan.ws['x'], blk.cross_attn
         N, hd, fa = self.num_heads, self.dim // self.num_heads, plan.fa
         layout = 'fused' if fa is None else 'seam'
         if ctx_layers[i] is None or ctx_layers[i].layout != layout:
             ctx_layers[i] = self._cross_kv(i, lin.lw, ctx_emb, layout)
-        kc, vc, _ = ctx_layers[i]
+        kvs = [(ctx_layers[i], ws['a'])]
+        if nag is not None:
+            _, neg_emb, neg_layers = nag
+            if neg_layers[i] is None or neg_layers[i].layout != layout:
+                neg_layers[i] = self._cross_kv(i, lin.lw, neg_emb, layout)
+            kvs.append((neg_layers[i], ws['q']))
         lin.ln('cross_attn.q', x, blk.norm3.weight, blk.norm3.bias, False)
         lin('cross_attn.q', ws['h'], ca.q.bias, ops.BIAS_BF16, ws['q'])
         ca.norm_rope_qk(ws['q'], None, ws['k'], None, prescale=fa is None)
-        if fa is not None:
-            # operator seam (1), reference model.py:176: flash_attention(q, k, v, k_lens=context_lens) with
-            # context_lens = None for T2V
-            y = fa(ws['k'].view(1, plan.L, N, hd), kc.view(1, -1, N, hd), vc.reshape(1, -1, N, hd), k_lens=None)
-            ws['a'].copy_(y.reshape(plan.L, self.dim))
-        elif self.cross_attn_head_sharded and self.sp_layout.size > 1:
-            self._cross_attention_head_sharded(ws, kc, vc)
-        else:
-            attend(ws['k'], kc, vc, ws['a'], self.text_len, N, hd, packed=True)
+        for (kc, vc, _), a in kvs:              # the prompt's into ws['a']; under NAG the negative prompt's into ws['q']
+            if fa is not None:
+                # operator seam (1), reference model.py:176: flash_attention(q, k, v, k_lens=context_lens) with
+                # context_lens = None for T2V
+                y = fa(ws['k'].view(1, plan.L, N, hd), kc.view(1, -1, N, hd), vc.reshape(1, -1, N, hd), k_lens=None)
+                a.copy_(y.reshape(plan.L, self.dim))
+            elif self.cross_attn_head_sharded and self.sp_layout.size > 1:
+                self._cross_attention_head_sharded(ws, kc, vc, a)
+            else:
+                attend(ws['k'], kc, vc, a, self.text_len, N, hd, packed=True)
+        if nag is not None:                     # per token over all its heads: behind head_to_seq on the head-sharded path
+            ops.nag_combine(ws['a'], ws['q'], ws['a'], *nag[0].params)
         lin('cross_attn.o', ws['a'], ca.o.bias, ops.GATE_RESID_F32, x)
 
-    def _cross_attention_head_sharded(self, ws, kc, vc):
+    def _cross_attention_head_sharded(self, ws, kc, vc, out):
         """model_seq.py:271-294: q through the seq->head all-to-all, K/V narrowed to this rank's heads (shrink_head),
-        attention over ALL tokens x local heads, head->seq all-to-all back.  Same values as the token-local form."""
+        attention over ALL tokens x local heads, head->seq all-to-all back into `out`.  Same values as the token-local form."""
         from ..distributed import ulysses
         U, ug, ur = self.sp_layout.U, self.sp_layout.uly_group, self.sp_layout.uly_rank
         N, hd = self.num_heads, self.dim // self.num_heads
@@ -820,7 +837,7 @@ class WanModel(nn.Module):
         else:
             ks, vs = kc[:, ur * nl * hd:(ur + 1) * nl * hd], vc[:, ur * nl * hd:(ur + 1) * nl * hd]
         attend(qg, ks, vs, ag, self.text_len, nl, hd, packed=True)
-        ulysses.head_to_seq(ag, ws['a'], ug, U, N, hd)
+        ulysses.head_to_seq(ag, out, ug, U, N, hd)
 
     # one forward: plan -> embed -> [step cache: open, skip exit] -> blocks -> [step cache: capture] -> head
     def _plan(self, lat, seq_len):
@@ -869,12 +886,12 @@ class WanModel(nn.Module):
         self._time_embedding(self._timesteps(t), ws['sin'], ws['e1'], ws['e'], ws['e0'])
         ops.add_rows(self.head.modulation.data.reshape(2, self.dim), ws['e'].reshape(1, self.dim), ws['hmod'], 1)
 
-    def _step_open(self, ws, ctx, reuse):
+    def _step_open(self, ws, ctx, reuse, nag=None):
         """step cache 1/3, behind the embedding -> the residual buffer of (this workspace, ctx).
         'compute' keeps the embedded stream in ws['xin'] ('reuse': the 'save' half's copy — the same latent, the same data)."""
         if self._step_mode[0] == 'skip':
             # 'reuse' finds x as the 'save' half embedded it: a skipped forward reads the stream and never writes it
-            resid = self._step_resid(ws, ctx, create=False)
+            resid = self._step_resid(ws, ctx, create=False, nag=nag)
             if resid is None:
                 raise RuntimeError("step_cache('skip'): no residual for this sequence length and context — a step_cache('compute') forward "
                                    'of the same context has to come first (weight changes and drop_step_cache() drop the residuals)')
@@ -884,9 +901,9 @@ class WanModel(nn.Module):
             ws['xin'] = torch.empty_like(ws['x'])
         if not reuse:
             ws['xin'].copy_(ws['x'])
-        return self._step_resid(ws, ctx, create=True)
+        return self._step_resid(ws, ctx, create=True, nag=nag)
 
-    def _step_capture(self, ws, ctx, resid):
+    def _step_capture(self, ws, ctx, resid, nag=None):
         """step cache 3/3, behind the last block: resid <- x - xin, what the blocks added to the stream, for the skipped steps that follow"""
         if not self._step_mode[1]:
             return ops.step_resid_capture(resid, ws['x'], ws['xin'])
@@ -894,29 +911,31 @@ class WanModel(nn.Module):
             ws['resid_stats'] = (torch.empty(2, dtype=torch.float64, device=resid.device), ops.step_resid_partials(resid.device))
         st, part = ws['resid_stats']
         ops.step_resid_capture(resid, ws['x'], ws['xin'], st, part)
-        self.step_cache_stats[self._ctx_key(ctx)] = tuple(st.tolist())
+        self.step_cache_stats[self._resid_key(ctx, nag)] = tuple(st.tolist())
 
-    def _block(self, i, blk, plan, mx, ctx_emb, ctx_layers, share):
-        """block i on the residual stream ws['x'] (reference model.py:297-311); mx: its quantised weights, None in bf16 mode"""
+    def _block(self, i, blk, plan, mx, ctx_emb, ctx_layers, share, nag=None):
+        """block i on the residual stream ws['x'] (reference model.py:297-311); mx: its quantised weights, None in bf16 mode;
+        nag: None, or (NAG, emb, layers) of the negative prompt for the cross-attention (_block_cross_attn)"""
         lin = _Linears(self._layer(i), mx, plan.ws, self.eps, self._mx_fuse)
         m = plan.ws['mod'][6 * i:6 * i + 6]
         self._block_self_attn(i, blk, plan, lin, m, share)
-        self._block_cross_attn(i, blk, plan, lin, ctx_emb, ctx_layers)
-        ws = plan.ws                            # ffn: x += gate * ffn.2(GELU(ffn.0(modulated LN(x))))
+        self._block_cross_attn(i, blk, plan, lin, ctx_emb, ctx_layers, nag)
+        ws = plan.ws                          # ffn: x += gate * ffn.2(GELU(ffn.0(modulated LN(x))))
         lin.ln('ffn.0', ws['x'], m[4], m[3], True)
         lin('ffn.0', ws['h'], blk.ffn['0'].bias, ops.BIAS_GELU_BF16, ws['u'])
         lin('ffn.2', ws['u'], blk.ffn['2'].bias, ops.GATE_RESID_F32, ws['x'], gate=m[5])
 
     @torch.no_grad()
-    def _forward_one(self, lat, t, ctx, seq_len, share=None):
+    def _forward_one(self, lat, t, ctx, seq_len, share=None, nag=None):
         """share: None, or the two halves of forward_pair — 'save' keeps the residual stream as it stands behind block 0's self-attention
-        (ws['x0']), 'reuse' starts from that copy instead of recomputing it (same latent, same t: nothing before that point reads `ctx`)."""
+        (ws['x0']), 'reuse' starts from that copy instead of recomputing it (same latent, same t: nothing before that point reads `ctx`).
+        nag: None, or (NAG, the negative prompt tensor of this sample) — normalized attention guidance in every cross-attention."""
         pk = self._pack()
         lat = lat.to(torch.float32).contiguous()
         plan = self._plan(lat, seq_len)
         ws, x = plan.ws, plan.ws['x']
         self._embed(plan, lat, t, patches=share != 'reuse')       # ('reuse': x comes back whole behind block 0's self-attention)
-        resid = self._step_open(ws, ctx, share == 'reuse') if self._step_mode else None
+        resid = self._step_open(ws, ctx, share == 'reuse', nag) if self._step_mode else None
         if resid is not None and self._step_mode[0] == 'skip':
             # step cache 2/3, the skip exit: no block runs — the residual the blocks added at this context's last computed step is added
             # again, inside the head's LayerNorm
@@ -925,11 +944,12 @@ class WanModel(nn.Module):
 
         ops.add_rows(pk['modulation'], ws['e0'], ws['mod'], 6)                       # model.py:292-295
         _, ctx_emb, ctx_layers = self._context(ctx)
+        nagb = None if nag is None else (nag[0], *self._context(nag[1])[1:])         # the negative prompt: embedded and cached like any prompt
         mxl = self._mx_layers() if self.gemm_precision == 'mxfp8' else None
         for i, blk in enumerate(self.blocks):
-            self._block(i, blk, plan, mxl[i] if mxl is not None else None, ctx_emb, ctx_layers, share)
+            self._block(i, blk, plan, mxl[i] if mxl is not None else None, ctx_emb, ctx_layers, share, nagb)
         if resid is not None:
-            self._step_capture(ws, ctx, resid)
+            self._step_capture(ws, ctx, resid, nag)
 
         # head (model.py:333-343): fp32 end to end
         ops.ln_modulate(x, ws['hmod'][1], ws['hmod'][0], True, self.eps, ws['hf'])
@@ -953,27 +973,51 @@ class WanModel(nn.Module):
         out = run()
         return run() if self._peer_transport_failed() else out
 
-    def forward(self, x, t, context, seq_len, clip_fea=None, y=None):
+    @staticmethod
+    def _checked_nag(nag, n):
+        """forward's nag= -> one (NAG, negative prompt tensor) per sample, or [None] * n"""
+        if nag is None:
+            return [None] * n
+        from ..utils.nag import NAG
+        try:
+            rule, negs = nag
+            negs = list(negs)
+        except (TypeError, ValueError):
+            raise ValueError(f'nag must be None or (NAG, [negative context tensors]), got {nag!r}') from None
+        if not isinstance(rule, NAG) or len(negs) != n or not all(torch.is_tensor(c) and c.dim() == 2 for c in negs):
+            raise ValueError(f'nag must be (wan.utils.nag.NAG, [one [len, text_dim] negative context tensor per sample: {n}]), got {nag!r}')
+        return [(rule, c) for c in negs]
+
+    def forward(self, x, t, context, seq_len, clip_fea=None, y=None, *, nag=None):
+        """nag (NOT part of the reference): None = the forward as it is, call for call; or (NAG, [negative context tensors]),
+        one tensor per sample — normalized attention guidance: every block's cross-attention runs a second time with the negative prompt's
+        K/V and ops.nag_combine mixes the two results per token in front of the `o` projection.  The negative prompt is embedded and its
+        K/V are made once and cached like any prompt's (the prompt cache holds 4 prompts; a guided call with NAG uses up to 3: the prompt,
+        the call's negative prompt and NAG's own if it differs).  In a step_cache scope the residual of a NAG forward is kept under
+        (prompt, negative prompt, (scale, tau, alpha)): a plain forward and a NAG forward of one prompt never share one."""
         if clip_fea is not None or y is not None:
             raise NotImplementedError('image conditioning (i2v) is not part of MoviiGen1.1 T2V')
+        nags = self._checked_nag(nag, len(context))
         t = t.reshape(-1)
-        return self._retry_without_peer_copies(lambda: [self._forward_one(u, t[i if t.numel() > 1 else 0], c, seq_len)
+        return self._retry_without_peer_copies(lambda: [self._forward_one(u, t[i if t.numel() > 1 else 0], c, seq_len, nag=nags[i])
                                                         for i, (u, c) in enumerate(zip(x, context))])
 
-    def forward_pair(self, x, t, context, context_null, seq_len):
+    def forward_pair(self, x, t, context, context_null, seq_len, *, nag=None):
         """The two guidance branches of ONE denoising step (reference text2video.py:237-240: two calls of the model on the same latent and t,
         with the prompt's and the negative prompt's embeddings) -> (cond, uncond), each what forward() returns for its context, bit for bit.
         Nothing in front of block 0's cross-attention reads the context — patch embedding, time embedding, and block 0's modulated LayerNorm,
         q|k|v projection, RMS-norm + RoPE, self-attention over all L tokens and its gated residual see the latent and t only — so the second
         branch starts from a copy of the first one's residual stream at that point (2.7 GB at 1920x832x81f) instead of computing it again:
         one self-attention launch and four GEMMs of 80 per step.  A replaced self-attention forward or a rebound flash_attention (the operator
-        seams) may be anything, also non-deterministic: then, and with MOVIIGEN_CFG_SHARED_PREFIX=0, the branches run as two plain forwards."""
+        seams) may be anything, also non-deterministic: then, and with MOVIIGEN_CFG_SHARED_PREFIX=0, the branches run as two plain forwards.
+        nag: as in forward(), for the conditional half only; the other half runs plain (block 0's shared prefix reads no context)."""
         plain = os.environ.get('MOVIIGEN_CFG_SHARED_PREFIX', '1') == '0' or _rebound_flash_attention() is not None or \
             _replaced_forward(self.blocks[0].self_attn) is not None or len(x) != 1 or len(context) != 1 or len(context_null) != 1
         if plain:
-            return self.forward(x, t, context, seq_len), self.forward(x, t, context_null, seq_len)
+            return self.forward(x, t, context, seq_len, nag=nag), self.forward(x, t, context_null, seq_len)
+        nag0 = self._checked_nag(nag, 1)[0]
         t = t.reshape(-1)
-        return self._retry_without_peer_copies(lambda: ([self._forward_one(x[0], t[0], context[0], seq_len, share='save')],
+        return self._retry_without_peer_copies(lambda: ([self._forward_one(x[0], t[0], context[0], seq_len, share='save', nag=nag0)],
                                                         [self._forward_one(x[0], t[0], context_null[0], seq_len, share='reuse')]))
 
 

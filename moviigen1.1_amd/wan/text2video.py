@@ -12,6 +12,7 @@ of `[len<=512, 4096]` tensors, and `input_prompt` / `n_prompt` may also be pre-c
 """
 import contextlib
 import gc
+import inspect
 import logging
 import math
 import os
@@ -28,6 +29,7 @@ from .utils.fm_solvers import FlowDPMSolverMultistepScheduler, get_sampling_sigm
 from .utils.fm_solvers_unipc import FlowUniPCMultistepScheduler
 from .utils.context_windows import ContextWindows
 from .utils.guidance import Guidance
+from .utils.nag import NAG
 from .utils.sample_plan import refuse_windows_with_step_cache, sample_plan
 from .utils.step_cache import resolve_plan
 
@@ -59,6 +61,21 @@ def _checked_windows(windows):
     if windows is not None and not isinstance(windows, ContextWindows):
         raise ValueError(f'windows must be None or a wan.utils.context_windows.ContextWindows, got {windows!r}')
     return windows
+
+
+def _checked_nag(nag, model=None):
+    """nag must be None or a NAG; given a model, that model's forward must take the `nag` keyword (a user's own `model=` may not)"""
+    if nag is not None and not isinstance(nag, NAG):
+        raise ValueError(f'nag must be None or a wan.utils.nag.NAG, got {nag!r}')
+    if nag is not None and model is not None:
+        fwd = getattr(model, 'forward', model)
+        try:
+            params = inspect.signature(fwd).parameters
+        except (TypeError, ValueError):
+            params = {}
+        if 'nag' not in params:
+            raise ValueError(f'nag needs a model whose forward takes the `nag` keyword (wan.modules.WanModel); {type(model).__name__} does not')
+    return nag
 
 
 def dit_seq_len(frames, h, w, patch_size, sp_size):
@@ -109,9 +126,10 @@ class WanT2V:
 
     def __init__(self, config, checkpoint_dir, device_id=0, rank=0, t5_fsdp=False, dit_fsdp=False, use_usp=False,
                  t5_cpu=False, text_encoder=None, model=None, vae=None, cfg_parallel=False, vae_parallel=False, use_ring=False, sp_degrees=None,
-                 dit_gemm='bf16', step_cache=None, guidance=None, windows=None, lora=None, lora_strength=1.0):
+                 dit_gemm='bf16', step_cache=None, guidance=None, windows=None, nag=None, lora=None, lora_strength=1.0):
         _checked_guidance(guidance)
         _checked_windows(windows)
+        _checked_nag(nag)
         self.device = torch.device(f'cuda:{device_id}')
         self.config = config
         self.rank = rank
@@ -187,6 +205,9 @@ class WanT2V:
         # the object's default for generate(windows=): None = the whole latent in one DiT pass (the reference's loop)
         self.windows = windows
         self.last_window_plan = None
+        # the object's default for generate(nag=): None = the cross-attention as it is (the reference's)
+        self.nag = nag
+        self.last_nag = None
 
     def _encode(self, prompt):
         if torch.is_tensor(prompt):
@@ -229,49 +250,57 @@ class WanT2V:
         assert torch.isfinite(z0).all().item(), 'the encoded init_video is not finite'
         return ops.lincomb(torch.empty_like(noise), [(z0, 1.0 - sigma), (noise, sigma)])
 
-    def _guidance_pair(self, latent, t, context, context_null, seq_len):
-        """(cond, uncond) noise predictions of one denoising step"""
+    def _guidance_pair(self, latent, t, context, context_null, seq_len, nag=None):
+        """(cond, uncond) noise predictions of one denoising step; nag: None, or what WanModel.forward(nag=) takes, for every forward of
+        the conditional context (the unconditional one runs plain)"""
+        kw = {} if nag is None else {'nag': nag}        # (None: the calls as they were, also for a model object without the keyword)
         pair = getattr(self.model, 'forward_pair', None)
         if self.cfgp is None and pair is not None:
             # both branches in one call: what they share (everything in front of block 0's cross-attention) is computed once,
             # the results are those of the two calls below bit for bit (WanModel.forward_pair)
-            cond, uncond = pair([latent], t, context, context_null, seq_len)
+            cond, uncond = pair([latent], t, context, context_null, seq_len, **kw)
             return cond[0], uncond[0]
         if self.cfgp is None:      # a model object without forward_pair: the reference's two calls (text2video.py:237-240)
-            cond = self.model([latent], t=t, context=context, seq_len=seq_len)[0]
+            cond = self.model([latent], t=t, context=context, seq_len=seq_len, **kw)[0]
             uncond = self.model([latent], t=t, context=context_null, seq_len=seq_len)[0]
             return cond, uncond
         # this half's branch only, then swap predictions with the partner rank
-        mine = self.model([latent], t=t, context=context_null if self.cfgp.branch else context, seq_len=seq_len)[0]
+        if self.cfgp.branch:
+            mine = self.model([latent], t=t, context=context_null, seq_len=seq_len)[0]
+        else:
+            mine = self.model([latent], t=t, context=context, seq_len=seq_len, **kw)[0]
         return self.cfgp.exchange(mine)
 
-    def _cond_prediction(self, latent, t, context, seq_len):
+    def _cond_prediction(self, latent, t, context, seq_len, nag=None):
         """the conditional branch alone, of a step outside the guidance interval: ONE forward — the call whose bits forward_pair promises for
         its cond half.  Under cfg_parallel both halves of the ranks run it (each its own Ulysses group) and nothing is exchanged."""
-        return self.model([latent], t=t, context=context, seq_len=seq_len)[0]
+        kw = {} if nag is None else {'nag': nag}
+        return self.model([latent], t=t, context=context, seq_len=seq_len, **kw)[0]
 
-    def _window_predictions(self, run, latent, t, context, context_null):
+    def _window_predictions(self, run, latent, t, context, context_null, nag=None):
         """the whole-clip (cond, uncond) predictions of one step through context windows (`run`: the call's WindowRun): every window in
         ascending order is cut out of the latent, predicted on its own at positions 0 .. Fw - 1 and blended into the whole-clip buffers.
-        context_null None: the conditional branch alone (a 'cond' step) -> (cond, None).  No host read."""
+        context_null None: the conditional branch alone (a 'cond' step) -> (cond, None).  No host read.  nag: one for every window."""
+        kw = {} if nag is None else {'nag': nag}
         for k, f0 in enumerate(run.plan.starts):
             ops.window_gather(latent, f0, run.lat)
             if context_null is None:
-                cond, uncond = self._cond_prediction(run.lat, t, context, run.seq_len), None
+                cond, uncond = self._cond_prediction(run.lat, t, context, run.seq_len, **kw), None
             else:
-                cond, uncond = self._guidance_pair(run.lat, t, context, context_null, run.seq_len)
+                cond, uncond = self._guidance_pair(run.lat, t, context, context_null, run.seq_len, **kw)
                 ops.window_blend(run.uncond, uncond, f0, run.w[k], run.first[k])
             ops.window_blend(run.cond, cond, f0, run.w[k], run.first[k])
         return run.cond, None if context_null is None else run.uncond
 
-    def _predictions(self, kind, latent, t, context, context_null, seq_len, wrun):
+    def _predictions(self, kind, latent, t, context, context_null, seq_len, wrun, nag=None):
         """(cond, uncond) of a 'guided' step, (cond, None) of a 'cond' step — the one call the sampling loop makes for a forward; wrun: the
-        call's WindowRun, None = the whole latent in one pass"""
+        call's WindowRun, None = the whole latent in one pass; nag: None, or (NAG, [negative context]) for the conditional forwards"""
+        kw = {} if nag is None else {'nag': nag}
         if wrun is not None:
-            return self._window_predictions(wrun, latent, t, context, context_null if kind == 'guided' else None)
+            return self._window_predictions(wrun, latent, t, context, context_null if kind == 'guided' else None, **kw)
         if kind == 'guided':
-            return self._guidance_pair(latent, t, context, context_null, seq_len)
-        return self._cond_prediction(latent, t, context, seq_len), None
+            return self._guidance_pair(latent, t, context, context_null, seq_len, **kw)
+        return self._cond_prediction(latent, t, context, seq_len, **kw), None
 
     def _scheduler(self, sample_solver, sampling_steps, shift):
         """-> (scheduler, timesteps on the device) of the reference's two solvers (text2video.py:186-207)"""
@@ -340,7 +369,7 @@ class WanT2V:
 
     def generate(self, input_prompt, size=(1280, 720), frame_num=81, shift=5.0, sample_solver='unipc',
                  sampling_steps=50, guide_scale=5.0, n_prompt="", seed=-1, offload_model=True,
-                 noise=None, callback=None, step_cache=None, guidance=None, windows=None, init_video=None, strength=1.0):
+                 noise=None, callback=None, step_cache=None, guidance=None, windows=None, nag=None, init_video=None, strength=1.0):
         """The reference's `generate` (text2video.py:114-271), plus a video-to-video start and a step cache that are NOT part of the reference:
 
         init_video: an existing clip to start from instead of pure noise — uint8 RGB frames [T, H0, W0, 3] of any size (tensor or array;
@@ -380,11 +409,22 @@ class WanT2V:
             forward per window, a 'zero' step none.  Scheduler step, masked_renoise, `callback(i, whole latent)`, decode and composite are
             unchanged: init_video, strength and `inpaint` work at any length.  The buffers and the device copies of the weights are
             allocated once per call; no host read in the loop.  Not together with a step cache (its residuals would be per window):
+            ValueError before any forward.
+
+        nag (default: the object's, WanT2V(nag=); None = off, the loop above call for call): a wan.utils.nag.NAG — normalized attention
+            guidance: a negative prompt that acts inside every cross-attention of every forward of the conditional context
+            (WanModel.forward(nag=)), so it also acts on the steps that run the conditional branch alone — a 'cond' step, each window of
+            one, the conditional half of a 'guided' step (under cfg_parallel: the half of the ranks that runs `input_prompt`).  The
+            negative prompt is nag.n_prompt (text or a pre-computed embedding, as n_prompt), or the call's n_prompt when that is None.
+            The unconditional half, the guidance mix, scheduler, masked_renoise, windows blend and decode are unchanged; a 'zero' step runs
+            nothing.  `self.last_nag` holds the NAG of the last call (None without).  A negative prompt at ONE forward per step:
+                generate(..., guidance=Guidance(interval=(0.0, 0.0)), nag=NAG(scale, n_prompt=...))
+            (no sigma of a schedule is 0, so every step is 'cond').  A `model=` object whose forward does not take the `nag` keyword:
             ValueError before any forward."""
         return self._sample(input_prompt=input_prompt, size=size, frame_num=frame_num, shift=shift, sample_solver=sample_solver,
                             sampling_steps=sampling_steps, guide_scale=guide_scale, n_prompt=n_prompt, seed=seed, offload_model=offload_model,
                             noise=noise, callback=callback, step_cache=step_cache, guidance=guidance, windows=windows,
-                            init_video=init_video, strength=strength)
+                            init_video=init_video, strength=strength, nag=nag)
 
     # `generate`'s arguments behind input_prompt with their defaults: what `inpaint` takes as keywords
     _GENERATE_DEFAULTS = dict(zip(generate.__code__.co_varnames[2:generate.__code__.co_argcount], generate.__defaults__))
@@ -420,7 +460,7 @@ class WanT2V:
     def inpaint(self, input_prompt, init_video, mask=None, keep_frames=0, strength=1.0, **kw):
         """Masked video-to-video (NOT part of the reference): keep part of `init_video` and regenerate the rest.  `kw` are `generate`'s other
         arguments (size, frame_num, shift, sample_solver, sampling_steps, guide_scale, n_prompt, seed, offload_model, noise, callback, step_cache,
-        guidance, windows).
+        guidance, windows, nag).
 
         mask: uint8 or bool, tensor or array, [Tm, H0, W0] (Tm == 1: one mask for every frame, or Tm >= frame_num: the first frame_num are used)
             or [H0, W0], with the spatial size of init_video (the frame size of uint8 frames, `size` for a float clip); >= 128 / True =
@@ -443,12 +483,13 @@ class WanT2V:
         return self._sample(edit=self.masked_edit(init_video, mask, keep_frames, args['size'], args['frame_num']), **args)
 
     def _sample(self, *, input_prompt, size, frame_num, shift, sample_solver, sampling_steps, guide_scale, n_prompt, seed, offload_model,
-                noise, callback, step_cache, guidance, windows, init_video, strength, edit=None):
+                noise, callback, step_cache, guidance, windows, init_video, strength, nag=None, edit=None):
         """the body of `generate` and `inpaint`, which hand it `generate`'s arguments by name; edit: None, or inpaint's MaskedEdit.
         Three parts: the arguments resolved and checked (no GPU), the tensors and the call's SamplePlan, the loop over plan.steps."""
         step_cache = self.step_cache if step_cache is None else step_cache
         guidance = _checked_guidance(self.guidance if guidance is None else guidance)
         windows = _checked_windows(self.windows if windows is None else windows)
+        nag = _checked_nag(self.nag if nag is None else nag, self.model)
         n_run, i0 = v2v_steps(sampling_steps, strength)
         if init_video is None and i0:
             raise ValueError('strength < 1 needs init_video: there is nothing to start from')
@@ -469,6 +510,9 @@ class WanT2V:
         seed_g.manual_seed(seed)
         context = self._encode(input_prompt)
         context_null = self._encode(n_prompt)
+        # NAG's negative prompt: its own, or the call's (already encoded); what every conditional forward of the loop is handed
+        nag_arg = None if nag is None else (nag, context_null if nag.n_prompt is None else self._encode(nag.n_prompt))
+        self.last_nag = nag
         if noise is None:
             noise = torch.randn(*target_shape, dtype=torch.float32, device=self.device, generator=seed_g)
         else:
@@ -503,7 +547,7 @@ class WanT2V:
                     pred = noise_pred.zero_()
                 else:                       # a 'cond' step's prediction is used as it is (a new tensor of every forward)
                     with self.model.step_cache(cache, stats=plan.stats) if cache else contextlib.nullcontext():     # (a 'skip' scope reads no stats)
-                        cond, uncond = self._predictions(kind, latent, t, context, context_null, seq_len, wrun)
+                        cond, uncond = self._predictions(kind, latent, t, context, context_null, seq_len, wrun, **({} if nag_arg is None else {'nag': nag_arg}))
                     pred = cond if kind == 'cond' else mix(noise_pred, uncond, cond)
                 latent = sample_scheduler.step(pred.unsqueeze(0), timesteps_host[i], latent.unsqueeze(0),
                                                return_dict=False, generator=seed_g)[0].squeeze(0)

@@ -24,7 +24,10 @@ without that calibration),
 guidance rescale; no values are recommended),
 `--context_frames N` / `--context_overlap M` / `--context_fuse pyramid|flat` (opt-in context windows, `WanT2V.generate(windows=)`,
 DESIGN.md §3.9: a `--frame_num` longer than one DiT pass is denoised as a whole through overlapping windows of N frames; no values are
-recommended) and
+recommended),
+`--nag_scale S` / `--nag_tau T` / `--nag_alpha A` / `--nag_negative TEXT` (opt-in normalized attention guidance, `WanT2V.generate(nag=)`,
+DESIGN.md §3.11: a negative prompt that acts inside every cross-attention, also on steps that run the conditional branch alone — with
+`--guide_interval 0,0` a negative prompt at one DiT forward per step; no values are recommended) and
 `--prompt_embeds FILE` (a torch file {'prompt': [len,4096], 'negative': [len,4096]} instead of running
 umT5 — for boxes without the tokenizer files)."""
 import argparse
@@ -119,6 +122,16 @@ FLAGS = [
                                help='with --context_frames: the frames two neighbouring windows share (a multiple of 4, below N).')),
     ('--context_fuse', dict(type=str, default='pyramid', choices=['pyramid', 'flat'],
                             help='with --context_frames: the weight of a frame inside its window when overlapping predictions are blended.')),
+    ('--nag_scale', dict(type=float, default=None, metavar='S',
+                         help='opt-in normalized attention guidance: every cross-attention is pushed away from the negative prompt by S in [1, 64] '
+                              '(one more short-key attention and one row-wise pass per block, no second DiT forward). Not the reference '
+                              'arithmetic; off by default.')),
+    ('--nag_tau', dict(type=float, default=None, metavar='T', help='with --nag_scale: the L1 norm of a pushed row is held at most T >= 1 times the '
+                                                                   "positive row's (default 2.5, the paper's).")),
+    ('--nag_alpha', dict(type=float, default=None, metavar='A', help='with --nag_scale: the weight A in [0, 1] of the pushed row in the blend with the '
+                                                                     "positive one (default 0.25, the paper's).")),
+    ('--nag_negative', dict(type=str, default=None, metavar='TEXT', help='with --nag_scale: the negative prompt of the attention guidance (default: the '
+                                                                         "call's negative prompt).")),
     ('--prompt_embeds', dict(type=str, default=None, help="torch file {'prompt','negative'} of umT5 embeddings, replaces the text encoder.")),
 ]
 
@@ -179,6 +192,19 @@ def _guidance_spec(args):
         raise AssertionError(f'--guide_interval / --cfg_zero_init / --guide_rescale: {e}') from None
 
 
+def _nag_spec(args):
+    """the four --nag_* flags -> WanT2V.generate's `nag` argument (None without --nag_scale)"""
+    if args.nag_scale is None:
+        assert args.nag_tau is None and args.nag_alpha is None and args.nag_negative is None, '--nag_tau / --nag_alpha / --nag_negative need --nag_scale'
+        return None
+    from wan.utils.nag import NAG
+    kw = {k: v for k, v in (('tau', args.nag_tau), ('alpha', args.nag_alpha), ('n_prompt', args.nag_negative)) if v is not None}
+    try:
+        return NAG(args.nag_scale, **kw)
+    except ValueError as e:
+        raise AssertionError(f'--nag_scale / --nag_tau / --nag_alpha: {e}') from None
+
+
 def _windows_spec(args):
     """the three --context_* flags -> WanT2V.generate's `windows` argument (None without --context_frames)"""
     if args.context_frames is None:
@@ -214,6 +240,7 @@ def _validate_args(args):
     args.step_cache_spec = _step_cache_spec(args)
     args.guidance = _guidance_spec(args)
     args.windows = _windows_spec(args)
+    args.nag = _nag_spec(args)
     assert args.size in SUPPORTED_SIZES[args.task], \
         f"Unsupport size {args.size} for task {args.task}, supported sizes are: {', '.join(SUPPORTED_SIZES[args.task])}"
 
@@ -301,6 +328,9 @@ def generate(args):
     if args.windows is not None:        # (likewise)
         v2v['windows'] = args.windows
         logging.info(f'context windows: {args.windows}')
+    if args.nag is not None:            # (likewise)
+        v2v['nag'] = args.nag
+        logging.info(f'normalized attention guidance: {args.nag}')
     run = pipe.generate
     if args.mask or args.keep_frames:       # masked video-to-video: the same call through WanT2V.inpaint
         v2v.update(mask=load_mask(args.mask) if args.mask else None, keep_frames=args.keep_frames)
