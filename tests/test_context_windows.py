@@ -10,13 +10,13 @@ import importlib.util
 import inspect
 import itertools
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import weights as W
+from abi_ref import header_declarations
 from context_windows_ref import blend_once_ref, blend_ref, gather_ref
 
 gpu = pytest.mark.gpu
@@ -109,18 +109,12 @@ def test_declarations():
     """header and ctypes table agree on the two functions; generate, inpaint, WanT2V and ops have the new surface"""
     from wan.backend import lib, ops
     from wan.text2video import WanT2V
-    hdr = open(os.path.join(ROOT, 'include', 'moviigen_hip.h')).read()
-    ctype = {'int': lib.c_int, 'int64_t': lib.c_i64, 'float': lib.c_f32}
+    decl = header_declarations()
     for name in NAMES:
-        m = re.search(r'^(int|int64_t)\s+' + name + r'\s*\(([^)]*)\)\s*;', hdr, re.M)
-        assert m, f'include/moviigen_hip.h does not declare {name}'
-        want = []
-        for arg in m.group(2).split(','):
-            arg = arg.strip()
-            if arg != 'void':
-                want.append(lib.c_vp if '*' in arg else ctype[arg.rsplit(' ', 1)[0].replace('const ', '')])
+        assert name in decl, f'include/moviigen_hip.h does not declare {name}'
+        restype, want = decl[name]
         assert lib.SIGNATURES[name] == want, name
-        assert m.group(1) == 'int' and name not in lib._RESTYPE
+        assert restype is lib.c_int and name not in lib._RESTYPE
     par = list(inspect.signature(WanT2V.generate).parameters)
     assert par[par.index('guidance') + 1] == 'windows' and par[-2:] == ['init_video', 'strength']
     assert inspect.signature(WanT2V.generate).parameters['windows'].default is None

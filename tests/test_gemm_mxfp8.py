@@ -3,7 +3,6 @@ GEMM (csrc/gemm_mxfp8.hip) against it, and WanModel.set_gemm_precision('mxfp8').
 import functools
 import math
 import os
-import re
 import sys
 
 import pytest
@@ -12,6 +11,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mxfp8_ref as R  # noqa: E402
 import weights as W  # noqa: E402
+from abi_ref import header_declarations  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 gpu = pytest.mark.gpu
@@ -71,10 +71,10 @@ def test_ref_scale_byte_table():
 
 def test_mxfp8_entry_points_are_declared():
     from wan.backend import lib
-    hdr = open(os.path.join(ROOT, 'include', 'moviigen_hip.h')).read()
+    decl = header_declarations()
     for name, nargs in (('mg_quant_mxfp8_rows', 9), ('mg_gemm_mxfp8', 17)):
         assert name in lib.SIGNATURES and len(lib.SIGNATURES[name]) == nargs
-        assert re.search(r'^int\s+' + name + r'\s*\(', hdr, re.M), name
+        assert name in decl and decl[name] == (lib.c_int, lib.SIGNATURES[name]), name
 
 
 # ------------------------------------------------------------------------------------------------

@@ -13,13 +13,13 @@ import importlib.util
 import inspect
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import weights as W
+from abi_ref import header_declarations
 from guidance_ref import coef_ref, combine_ref, stats_ref, variances
 
 gpu = pytest.mark.gpu
@@ -61,18 +61,12 @@ def test_declarations():
     """header and ctypes table agree on the four functions; generate, inpaint, WanT2V and the launcher have the new surface"""
     from wan.backend import lib
     from wan.text2video import WanT2V
-    hdr = open(os.path.join(ROOT, 'include', 'moviigen_hip.h')).read()
-    ctype = {'int': lib.c_int, 'int64_t': lib.c_i64, 'float': lib.c_f32}
+    decl = header_declarations()
     for name in NAMES:
-        m = re.search(r'^(int|int64_t)\s+' + name + r'\s*\(([^)]*)\)\s*;', hdr, re.M)
-        assert m, f'include/moviigen_hip.h does not declare {name}'
-        want = []
-        for arg in m.group(2).split(','):
-            arg = arg.strip()
-            if arg != 'void':
-                want.append(lib.c_vp if '*' in arg else ctype[arg.rsplit(' ', 1)[0].replace('const ', '')])
-        assert lib.SIGNATURES[name] == want, name
-        assert (m.group(1) == 'int64_t') == (lib._RESTYPE.get(name) is lib.ctypes.c_int64), name
+        assert name in decl, f'include/moviigen_hip.h does not declare {name}'
+        restype, want = decl[name]
+        assert restype in (lib.c_int, lib.c_i64) and lib.SIGNATURES[name] == want, name
+        assert (restype is lib.c_i64) == (lib._RESTYPE.get(name) is lib.ctypes.c_int64), name
     assert inspect.signature(WanT2V.generate).parameters['guidance'].default is None
     assert inspect.signature(WanT2V.__init__).parameters['guidance'].default is None
     inspect.signature(WanT2V.inpaint).bind(None, 'prompt', 'clip', guidance=None)

@@ -41,6 +41,21 @@ def test_cabi_exports_every_declared_symbol():
         assert exported == want, (path, exported ^ want)      # nothing undeclared leaks out, nothing declared is missing
 
 
+def test_cabi_tables_match_every_declaration():
+    """every function include/moviigen_hip.h declares against lib.SIGNATURES / SIGNATURES_AB / _RESTYPE: the same names, the same
+    argument types in the same order, the same return type (a wrong entry is silent memory corruption, not an error)."""
+    from abi_ref import header_declarations
+    from wan.backend import lib
+    decl = header_declarations()
+    table = {**lib.SIGNATURES, **lib.SIGNATURES_AB}
+    assert len(lib.SIGNATURES) + len(lib.SIGNATURES_AB) == len(table) >= 80
+    assert set(decl) == set(table), set(decl) ^ set(table)
+    assert set(lib._RESTYPE) <= set(table), set(lib._RESTYPE) - set(table)
+    for name, (restype, argtypes) in decl.items():
+        assert table[name] == argtypes, name
+        assert lib._RESTYPE.get(name, lib.c_int) is restype, name
+
+
 def test_ab_library_switches_refuse_unknown_numbers():
     """the A/B library's kernel-selection switches are host-side bookkeeping (no GPU needed): numbers that name a kernel or a measurement build are
     accepted, everything else is refused with MG_ERR_ARG instead of being aliased to some kernel; the scope resets them."""

@@ -8,13 +8,13 @@ three passes bit for bit against torch.where / the plain-loop restatement; inpai
 """
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import weights as W
+from abi_ref import header_declarations
 from mask_ref import latent_footprint, mask_from_u8_ref, mask_to_latent_ref
 
 gpu = pytest.mark.gpu
@@ -56,16 +56,11 @@ def test_declarations():
     """header and ctypes table agree on the four functions; generate keeps its signature, inpaint and the launcher have the new surface."""
     from wan.backend import lib
     from wan.text2video import WanT2V
-    hdr = open(os.path.join(ROOT, 'include', 'moviigen_hip.h')).read()
-    ctype = {'int': lib.c_int, 'int64_t': lib.c_i64, 'float': lib.c_f32}
+    decl = header_declarations()
     for name in NAMES:
-        m = re.search(r'^int\s+' + name + r'\s*\(([^)]*)\)\s*;', hdr, re.M)
-        assert m, f'include/moviigen_hip.h does not declare {name}'
-        want = []
-        for arg in m.group(1).split(','):
-            arg = arg.strip()
-            want.append(lib.c_vp if '*' in arg else ctype[arg.rsplit(' ', 1)[0].replace('const ', '')])
-        assert lib.SIGNATURES[name] == want, name
+        assert name in decl, f'include/moviigen_hip.h does not declare {name}'
+        restype, want = decl[name]
+        assert restype is lib.c_int and lib.SIGNATURES[name] == want, name
     par = inspect.signature(WanT2V.generate).parameters
     assert list(par)[-2:] == ['init_video', 'strength'] and par['init_video'].default is None and par['strength'].default == 1.0
     par = inspect.signature(WanT2V.inpaint).parameters

@@ -9,7 +9,6 @@ leaves the second-order terms room) and ONE correct rounding to the storage type
 """
 import inspect
 import os
-import re
 import sys
 
 import pytest
@@ -17,6 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import weights as W  # noqa: E402
+from abi_ref import header_declarations  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 gpu = pytest.mark.gpu
@@ -63,15 +63,10 @@ def test_declarations():
     """header and ctypes table agree on mg_lora_merge; WanT2V and the launcher have the new surface."""
     from wan.backend import lib
     from wan.text2video import WanT2V
-    hdr = open(os.path.join(ROOT, 'include', 'moviigen_hip.h')).read()
-    m = re.search(r'^int\s+mg_lora_merge\s*\(([^)]*)\)\s*;', hdr, re.M)
-    assert m, 'include/moviigen_hip.h does not declare mg_lora_merge'
-    ctype = {'int': lib.c_int, 'int64_t': lib.c_i64, 'float': lib.c_f32}
-    want = []
-    for arg in m.group(1).split(','):
-        arg = ' '.join(arg.split())
-        want.append(lib.c_vp if '*' in arg else ctype[arg.rsplit(' ', 1)[0].replace('const ', '')])
-    assert lib.SIGNATURES['mg_lora_merge'] == want
+    decl = header_declarations()
+    assert 'mg_lora_merge' in decl, 'include/moviigen_hip.h does not declare mg_lora_merge'
+    restype, want = decl['mg_lora_merge']
+    assert restype is lib.c_int and lib.SIGNATURES['mg_lora_merge'] == want
     assert len(want) == 11
     par = inspect.signature(WanT2V.__init__).parameters
     assert list(par)[-2:] == ['lora', 'lora_strength']           # appended: every positional call keeps its meaning

@@ -4,7 +4,6 @@ reference quantiser (tests/mxfp8_ref.py) — bit for bit, and WanModel's 'mxfp8'
 import ctypes
 import functools
 import os
-import re
 import sys
 import types
 
@@ -14,6 +13,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mxfp8_ref as R  # noqa: E402
 import weights as W  # noqa: E402
+from abi_ref import header_declarations  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 gpu = pytest.mark.gpu
@@ -30,13 +30,11 @@ def dev():
 # ------------------------------------------------------------------------------------------------
 def test_fused_entry_points_are_declared():
     from wan.backend import lib
-    hdr = open(os.path.join(ROOT, 'include', 'moviigen_hip.h')).read()
-    product = hdr.split('#ifdef MG_AB_BUILD')[0]
+    decl = header_declarations()
     for name, nargs in (('mg_ln_modulate_mxfp8', 16), ('mg_gemm_mxfp8_gelu_q', 17)):
-        assert name in lib.SIGNATURES and len(lib.SIGNATURES[name]) == nargs
-        m = re.search(r'^int\s+' + name + r'\s*\(([^;]*)\)\s*;', product, re.M)
-        assert m, name
-        assert len(m.group(1).split(',')) == nargs
+        assert name in lib.SIGNATURES and len(lib.SIGNATURES[name]) == nargs       # (SIGNATURES: the product section's table)
+        assert name in decl, name
+        assert decl[name] == (lib.c_int, lib.SIGNATURES[name]) and len(decl[name][1]) == nargs
 
 
 # ------------------------------------------------------------------------------------------------

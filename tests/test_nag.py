@@ -12,13 +12,13 @@ import functools
 import importlib.util
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import weights as W
+from abi_ref import header_declarations
 from nag_ref import dit_forward_nag, nag_rows
 
 gpu = pytest.mark.gpu
@@ -68,11 +68,10 @@ def test_declarations():
     from wan.modules import WanModel
     from wan.text2video import WanT2V
     hdr = open(os.path.join(ROOT, 'include', 'moviigen_hip.h')).read()
-    ctype = {'int': lib.c_int, 'int64_t': lib.c_i64, 'float': lib.c_f32}
-    m = re.search(r'^int\s+' + NAME + r'\s*\(([^)]*)\)\s*;', hdr, re.M)
-    assert m, f'include/moviigen_hip.h does not declare {NAME}'
-    want = [lib.c_vp if '*' in a else ctype[a.strip().rsplit(' ', 1)[0].replace('const ', '')] for a in m.group(1).split(',')]
-    assert lib.SIGNATURES[NAME] == want and len(want) == 12 and NAME not in lib._RESTYPE
+    decl = header_declarations()
+    assert NAME in decl, f'include/moviigen_hip.h does not declare {NAME}'
+    restype, want = decl[NAME]
+    assert restype is lib.c_int and lib.SIGNATURES[NAME] == want and len(want) == 12 and NAME not in lib._RESTYPE
     assert hdr.index(NAME) < hdr.index('#ifdef MG_AB_BUILD')                 # the product section
     assert list(inspect.signature(ops.nag_combine).parameters) == ['zp', 'zn', 'out', 'scale', 'tau', 'alpha']
     for fn in (WanT2V.generate, WanT2V.__init__):

@@ -18,11 +18,11 @@ import math
 import pytest
 import torch
 
+from sentinels import FILL, FILL16, holds16, host, rejects, sentinel16
+
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24          # unit roundoff of fp32
-FILL = 123.0            # what the rejection cases fill their parents with
-FILL16 = 0x5A5A         # the same for bf16 buffers, as a bit pattern
 
 
 @pytest.fixture(scope='module')
@@ -57,34 +57,11 @@ def eq16(a, b):
     return a.shape == b.shape and torch.equal(a.cpu().contiguous().view(torch.int16), b.cpu().contiguous().view(torch.int16))
 
 
-def sentinel16(shape, dev):
-    return torch.full(tuple(shape), FILL16, dtype=torch.int16, device=dev).view(torch.bfloat16)
-
-
-def holds16(t):
-    return bool((t.view(torch.int16) == FILL16).all())
-
-
 def within(out, ref64, n, mag64):
     """the DERIVED bound, elementwise"""
     err = (out.detach().cpu().double() - ref64).abs()
     bound = n * U * mag64
     assert bool((err <= bound).all()), f'max err/bound {(err / bound).max().item():.3f} (n = {n})'
-
-
-def rejects(ops_call, *parents):
-    """ops_call raises MoviigenHipError and no parent buffer changed"""
-    from wan.backend import lib
-    with pytest.raises(lib.MoviigenHipError):
-        ops_call()
-    torch.cuda.synchronize()
-    for p in parents:
-        assert holds16(p) if p.dtype == torch.bfloat16 else bool((p == FILL).all()), 'a rejected call wrote to its output'
-
-
-def host(t):
-    """the tensor in pinned host memory: not a CUDA tensor for the wrapper, yet memory the device may touch"""
-    return t.cpu().pin_memory()
 
 
 # ------------------------------------------------------------------------------------------------

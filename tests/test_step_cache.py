@@ -8,13 +8,13 @@ n x 2^-53 relative: all terms are non-negative, so every summation order of n te
 import importlib.util
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import weights as W
+from abi_ref import header_declarations
 
 gpu = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -124,17 +124,12 @@ def test_declarations():
     """header and ctypes table agree on the new entries; generate and the constructor have the argument, default off."""
     from wan.backend import lib
     from wan.text2video import WanT2V
-    hdr = open(os.path.join(ROOT, 'include', 'moviigen_hip.h')).read()
-    ctype = {'int': lib.c_int, 'int64_t': lib.c_i64, 'float': lib.c_f32}
+    decl = header_declarations()
     for name, n_args in (('mg_step_resid_capture_f32', 7), ('mg_resid_ln_modulate_f32', 12)):
-        m = re.search(r'^int\s+' + name + r'\s*\(([^)]*)\)\s*;', hdr, re.M)
-        assert m, name
-        want = []
-        for arg in m.group(1).split(','):
-            arg = ' '.join(arg.split())
-            want.append(lib.c_vp if '*' in arg else ctype[arg.rsplit(' ', 1)[0].replace('const ', '')])
-        assert lib.SIGNATURES[name] == want and len(want) == n_args
-    assert re.search(r'^int64_t\s+mg_step_resid_partials_bytes\s*\(void\)\s*;', hdr, re.M)
+        assert name in decl, name
+        restype, want = decl[name]
+        assert restype is lib.c_int and lib.SIGNATURES[name] == want and len(want) == n_args
+    assert decl['mg_step_resid_partials_bytes'] == (lib.c_i64, [])
     assert lib.SIGNATURES['mg_step_resid_partials_bytes'] == [] and lib._RESTYPE['mg_step_resid_partials_bytes'] is lib.c_i64
     assert inspect.signature(WanT2V.generate).parameters['step_cache'].default is None
     assert inspect.signature(WanT2V.__init__).parameters['step_cache'].default is None

@@ -9,7 +9,6 @@ of the tensor scale: the bound the exact encode and the fast decode are held to)
 """
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
@@ -17,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 import weights as W
+from abi_ref import header_declarations
 from resize_ref import axis_weights, cover_geometry, resize_f64, video_from_u8_f64
 
 gpu = pytest.mark.gpu
@@ -53,15 +53,10 @@ def test_declarations():
     from wan.text2video import WanT2V
     from wan.utils import FlowDPMSolverMultistepScheduler, FlowUniPCMultistepScheduler
     from wan.utils.utils import load_video
-    hdr = open(os.path.join(ROOT, 'include', 'moviigen_hip.h')).read()
-    m = re.search(r'^int\s+mg_video_from_u8\s*\(([^)]*)\)\s*;', hdr, re.M)
-    assert m, 'include/moviigen_hip.h does not declare mg_video_from_u8'
-    ctype = {'int': lib.c_int, 'int64_t': lib.c_i64, 'float': lib.c_f32}
-    want = []
-    for arg in m.group(1).split(','):
-        arg = arg.strip()
-        want.append(lib.c_vp if '*' in arg else ctype[arg.rsplit(' ', 1)[0].replace('const ', '')])
-    assert lib.SIGNATURES['mg_video_from_u8'] == want
+    decl = header_declarations()
+    assert 'mg_video_from_u8' in decl, 'include/moviigen_hip.h does not declare mg_video_from_u8'
+    restype, want = decl['mg_video_from_u8']
+    assert restype is lib.c_int and lib.SIGNATURES['mg_video_from_u8'] == want
     par = inspect.signature(WanT2V.generate).parameters
     assert par['init_video'].default is None and par['strength'].default == 1.0
     assert list(par)[-2:] == ['init_video', 'strength']          # appended: every positional call of the reference keeps its meaning
